@@ -13,9 +13,16 @@ an RCCL all-reduce of those 4 sums.  Workload at N=1: BASELINE.json configs[2] (
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W          (no launcher: bench.py starts the N ranks itself, `self_launch`)
 
-Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel (largest share of GPU time in the
-timed region), measured live with HIP events on the launch stream; `cpu_baseline` is the CPU oracle (a port
-of the reference algorithm, oracle/tfgridnet_oracle.py) timed on this box's host cores on a bounded sample.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) and nothing else.  `--full` adds the
+rest: `roofline` describes the dominant kernel (largest share of GPU time in the timed region), measured live with
+HIP events on the launch stream; `power`, `secondary` (the other BASELINE configurations); `cpu_baseline` is the
+CPU oracle (a port of the reference algorithm, oracle/tfgridnet_oracle.py) timed on this box's host cores on a
+bounded sample, with `parity` against it; `gpu_library_baseline`; for N > 1 the all-reduce by itself.
+
+`--dump-outputs DIR` writes what the last timed step computed, as DIR/<name>.npy (float32 / float64, at most
+64 MB in all; a larger output is replaced by a fixed, seeded sample of its rows plus `<name>_rows.npy`).  The
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -78,6 +85,36 @@ EMBED_QK = 4 * 1251 * 520 * 4.0
 EMBED_CALL_BYTES = {"lh_emb_axis.intra": 6 * EMBED_AE, "lh_emb_axis.inter": 6 * EMBED_AE,
                     "lh_emb_attn_block": 6 * EMBED_AE + 4 * EMBED_QK, "lh_emb_head": EMBED_AE,
                     "lh_emb_frontend": 2 * EMBED_AE}
+
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: all arrays of one run together
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: each of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 kept, everything else float32.
+    Past `limit` bytes in all, the largest arrays are cut to a fixed, seeded sample of their rows (first axis, sorted,
+    numpy seed 0) and the row indices go to <name>_rows.npy (float64)."""
+    import numpy as np
+    arrs = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrs[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    for k in sorted(arrs, key=lambda k: -arrs[k].nbytes):
+        if total <= limit:
+            break
+        a = arrs[k]
+        if a.ndim == 0 or a.shape[0] < 2:
+            continue
+        row = a.nbytes // a.shape[0]
+        keep = max(1, (limit - (total - a.nbytes)) // (row + 8))
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], min(keep, a.shape[0]), replace=False))
+        arrs[k], arrs[k + "_rows"] = np.ascontiguousarray(a[rows]), rows.astype(np.float64)
+        total += arrs[k].nbytes + arrs[k + "_rows"].nbytes - a.nbytes
+    assert total <= limit, f"--dump-outputs: {total} bytes after sampling, limit {limit}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
 
 PACKAGE_POWER_CAP_W = 1400.0          # MI355X package power limit (rocm-smi --showmaxpower on the bench boxes)
 MEASURED_MFMA16_TFLOPS_AT_CAP = 2310.0   # pure v_mfma_f32_16x16x32_f16 stream, every CU, non-trivial operands: 1280 W at
@@ -376,6 +413,8 @@ def bench_stream(args, net, dev, rank, world):
         lat.append(time.perf_counter() - t1)
     elapsed = time.perf_counter() - t0
     lat.sort()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"separated_chunk": y})      # the last timed chunk's output
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         print(json.dumps({
@@ -478,6 +517,8 @@ def bench_embed(args, dev, rank, world, dist):
     elapsed = float(el.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embedding": emb})
     roof = embed_roofline(kern, B)
     cpu, parity = None, None
     if not args.no_cpu_baseline:
@@ -539,6 +580,8 @@ def bench_render(args, dev, rank, world, dist):
     elapsed = float(el.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("mixture", "target", "norm_factor", "events"), out)))
     call_ms = e0.elapsed_time(e1) / args.steps
     flops = 2.0 * N * Lh * S1 * 2 * B                       # FIR MACs x 2 (upper bound: ignores the start-up triangle)
     bytes_ = (S1 * N + S1 * 2 * N * 3 + 2 * 2 * N) * 4.0 * B  # src in, events out + 2 reads by the mix, mixture + target out
@@ -612,9 +655,12 @@ def dry_run_cpu(args, rank, world):
     for _ in range(args.warmup):
         step()
     elapsed, _, sums = timed_region(step, args.steps, dist if world > 1 else None, "cpu", lambda: None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"metric_sums": sums})
     ranks_seen, allreduce_us = world, None
-    if world > 1:                        # same fields as the GPU line: the group's own size, the exchange step by itself
+    if world > 1:                        # same fields as the GPU line: the group's own size, the exchange step by itself (--full)
         ranks_seen = dist.get_world_size()
+    if world > 1 and args.full:
         buf = sums.clone()
         t0 = time.perf_counter()
         for _ in range(20):
@@ -919,24 +965,27 @@ def secondary_measurements(net, dev, mix8, emb8):
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` (N > 1) WITHOUT a launcher around it: replace this process with
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same
+    """`python bench.py --gpus N` (N > 1) WITHOUT a launcher around it: run, as a child process, and
+    exit with its status, `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same
     arguments>` — the command the contract names, one rank per GPU; the ranks then take the `WORLD_SIZE` branch of `main`.
     Under an external torchrun (RANK / WORLD_SIZE set) this is never reached."""
     import socket
     if "--dry-run-cpu" not in sys.argv and torch.cuda.device_count() < n:
         sys.exit(f"bench.py --gpus {n}: only {torch.cuda.device_count()} GPU(s) visible on this node")
+    import subprocess
     with socket.socket() as s_:                                     # a free rendezvous port on the loopback interface
         s_.bind(("127.0.0.1", 0))
         port = s_.getsockname()[1]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC for RCCL (task environment)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("OMP_NUM_THREADS", str(max(1, len(os.sched_getaffinity(0)) // n)))
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")               # dmabuf IPC for RCCL (task environment)
+    env.setdefault("MASTER_ADDR", "127.0.0.1")
+    env.setdefault("OMP_NUM_THREADS", str(max(1, len(os.sched_getaffinity(0)) // n)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    print(f"[bench] --gpus {n} without a launcher: exec {' '.join(cmd[1:9])} ...", file=sys.stderr, flush=True)
+    print(f"[bench] --gpus {n} without a launcher: running {' '.join(cmd[1:9])} ...", file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a child process, not exec: this process may already hold the GPU runtime (device_count above)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -961,6 +1010,12 @@ def main():
     ap.add_argument("--time-chunks", type=int, default=None,
                     help="override Net.time_chunks: windows of the time axis run on as many HIP streams (A/B runs; 1 = off)")
     ap.add_argument("--tune", default="", help="comma list key=value for lh_set_tuning (A/B runs), e.g. 0=2,1=1")
+    ap.add_argument("--full", action="store_true",
+                    help="offline mode: everything beyond the headline too — per-call breakdown and roofline of the dominant "
+                         "call, power leg, secondary configurations, CPU baseline + parity, GPU-library baseline, N > 1 "
+                         "all-reduce by itself (the --no-* switches trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -1033,31 +1088,38 @@ def main():
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
-        # one fully instrumented step (HIP events around every C-ABI call): the per-call breakdown, and which call
-        # dominates.  The timed region then brackets only the dominant call's launches with events, so the 27 calls of a
-        # step are not separated by 54 event records.
-        net._prof = []
-        step()
-        torch.cuda.synchronize()
-        breakdown = durations(net._prof)
-        dom = max(breakdown, key=lambda k: breakdown[k]["total_ms"])
-        log(f"warm-up done; dominant call {dom}")
-        # Sampled: every 4th call of the dominant entry point is bracketed (3 calls per step, so the samples rotate through
-        # the three blocks).  A HIP event record is not free on the stream: the dispatch timeline of a step showed a 5.6-6.3 us
-        # idle gap at each of the six records of a fully bracketed step (profiles/r05o_b32_step_timeline.txt: 35 us = 0.5 % of
-        # the step was the measurement itself); sampled, the bracket costs ~9 us per step.
-        net._prof, net._prof_only, net._prof_stride, net._prof_count = [], {dom}, int(os.environ.get("LOOKONCE_BENCH_EVENT_STRIDE", "4")), {}
+        if args.full:
+            # one fully instrumented step (HIP events around every C-ABI call): the per-call breakdown, and which call
+            # dominates.  The timed region then brackets only the dominant call's launches with events, so the 27 calls of a
+            # step are not separated by 54 event records.
+            net._prof = []
+            step()
+            torch.cuda.synchronize()
+            breakdown = durations(net._prof)
+            dom = max(breakdown, key=lambda k: breakdown[k]["total_ms"])
+            log(f"warm-up done; dominant call {dom}")
+            # Sampled: every 4th call of the dominant entry point is bracketed (3 calls per step, so the samples rotate through
+            # the three blocks).  A HIP event record is not free on the stream: the dispatch timeline of a step showed a 5.6-6.3 us
+            # idle gap at each of the six records of a fully bracketed step (profiles/r05o_b32_step_timeline.txt: 35 us = 0.5 % of
+            # the step was the measurement itself); sampled, the bracket costs ~9 us per step.
+            net._prof, net._prof_only, net._prof_stride, net._prof_count = [], {dom}, int(os.environ.get("LOOKONCE_BENCH_EVENT_STRIDE", "4")), {}
         elapsed, local_elapsed, (y, sums) = timed_region(step, args.steps, dist, dev, torch.cuda.synchronize)
-        prof, net._prof, net._prof_only, net._prof_stride = net._prof, None, None, 1
-        roof_samples = len(prof)
+        if args.full:
+            prof, net._prof, net._prof_only, net._prof_stride = net._prof, None, None, 1
+            roof_samples = len(prof)
     log(f"timed region: {local_elapsed * 1e3 / args.steps:.3f} ms/step (max over ranks {elapsed * 1e3 / args.steps:.3f})")
     # the forwards ran asynchronously (deferred range check, net.py): one look at this Net's flag word for the whole region
     range_flag_raised = bool(net.range_status(dev)) if net.range_check else None
     assert not range_flag_raised, "LH_ERR_RANGE: a timed forward stored zeros in place of non-finite samples"
-    # N > 1: the exchange step by itself — 100 all-reduces of the 32-byte metric vector on RCCL, HIP events on this rank
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step: the separated waveforms [B, 2, N] and the
+        # (all-reduced) metric sums
+        dump_outputs(args.dump_outputs, {"separated": y, "metric_sums": sums})
     allreduce_us, ranks_seen = None, world
     if dist is not None:
         ranks_seen = dist.get_world_size()
+    # N > 1: the exchange step by itself (--full) — 100 all-reduces of the 32-byte metric vector on RCCL, HIP events on this rank
+    if dist is not None and args.full:
         buf = sums.clone()
         for _ in range(10):
             dist.all_reduce(buf)
@@ -1070,77 +1132,22 @@ def main():
         torch.cuda.synchronize()
         allreduce_us = e0.elapsed_time(e1) * 10.0
     power = None
-    if world == 1 and not args.no_power:
+    if args.full and world == 1 and not args.no_power:
         with torch.no_grad():
             power = power_leg(step)
         log(f"power leg: {power}")
 
-    # HIP-event durations (this rank): the dominant call live over the timed region, the others from the instrumented
-    # warm-up step
-    kern = dict(breakdown)
-    kern.update(durations(prof))
-    gpu_ms = sum(v["avg_ms"] * breakdown[k]["launches"] for k, v in kern.items())
+    if args.full:
+        # HIP-event durations (this rank): the dominant call live over the timed region, the others from the instrumented
+        # warm-up step
+        kern = dict(breakdown)
+        kern.update(durations(prof))
+        gpu_ms = sum(v["avg_ms"] * breakdown[k]["launches"] for k, v in kern.items())
 
     if rank == 0:
         total_clips = world * B * args.steps
         value = total_clips * FRAMES_PER_CLIP / elapsed
         ms_per_step = elapsed / args.steps * 1e3
-        w = KERNEL_WORK[dom]
-        traffic, traffic_src, tj_dom = None, None, None
-        tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")     # HBM bytes per launch from the PMC passes
-        if os.path.exists(tfile):
-            tj = json.load(open(tfile))
-            if tj.get("batch_per_gpu") == B and dom in tj.get("kernels", {}):
-                tj_dom = tj["kernels"][dom]
-                traffic = tj["kernels"][dom]["hbm_bytes_per_launch"]    # per kernel launch (rocprofv3 dispatch)
-                traffic_src = ("profiles/pmc_traffic.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                               "bench, committed with the kernels; source profile: %s) — not re-measured in this run"
-                               % tj.get("source", "see profiles/README.md"))
-        if w["bound"] == "mfma":
-            ach = w["flops"] * B / (kern[dom]["avg_ms"] * 1e-3) / 1e12
-            peak = PEAK_F16_MFMA_TFLOPS if net.gemm_mode == "f16x3" else PEAK_FP32_MFMA_TFLOPS
-            roof = dict(kernel=dom, bound="mfma", achieved=ach, peak=peak, unit="TFLOP/s", frac=ach / peak,
-                        traffic=traffic,
-                        note=("algorithmic fp32-equivalent FLOPs; f16x3 mode executes 3x as many fp16 MFMA FLOPs, "
-                              "peak = dense fp16 MFMA") if net.gemm_mode == "f16x3" else "exact fp32 MFMA")
-        else:
-            ach = w["bytes"] * B / (kern[dom]["avg_ms"] * 1e-3) / 1e9
-            roof = dict(kernel=dom, bound="hbm", achieved=ach, peak=PEAK_HBM_GBS, unit="GB/s",
-                        frac=ach / PEAK_HBM_GBS, traffic=traffic)
-        lpc = LAUNCHES_PER_CALL.get(dom, 1)
-        roof["traffic_source"] = traffic_src
-        roof["kernel_function"] = KERNEL_NAME.get(dom, dom)
-        roof["launches_per_call"] = lpc            # achieved = work of one call / duration of one call (= per launch too)
-        roof["avg_call_ms"] = kern[dom]["avg_ms"]
-        roof["event_samples"] = roof_samples       # calls of the dominant entry point bracketed with HIP events in the timed region
-        roof["avg_launch_ms"] = kern[dom]["avg_ms"] / lpc
-        # the same call in the fully instrumented warm-up step (event pairs around every call, as rocprofv3's tracer
-        # also separates the dispatches): the figure to hold against profiles/*kernel_stats*.csv
-        roof["avg_launch_ms_instrumented_step"] = breakdown[dom]["avg_ms"] / lpc
-        roof["share_of_gpu_time"] = kern[dom]["avg_ms"] * breakdown[dom]["launches"] / gpu_ms
-        # the same kernel against the other roofline, and against what the chip sustains under its 1400 W package limit
-        roof["frac_hbm"] = w["bytes"] * B / (kern[dom]["avg_ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS
-        if w["bound"] == "mfma" and net.gemm_mode == "f16x3":
-            roof["executed_fp16_tflops"] = 3.0 * roof["achieved"]
-            roof["frac_of_measured_mfma_rate_at_power_cap"] = 3.0 * roof["achieved"] / MEASURED_MFMA16_TFLOPS_AT_CAP
-        if tj_dom is not None:
-            for k_ in ("mfma_busy", "valu_busy"):
-                if k_ in tj_dom:
-                    roof[k_] = tj_dom[k_]
-            if "ratio_to_survey_8d_per_call" in tj_dom:     # the contract's byte count for the stage (2 A), next to the kernel's own
-                roof["traffic_ratio_to_survey_8d_stage_bytes"] = tj_dom["ratio_to_survey_8d_per_call"]
-                roof["traffic_note"] = ("traffic = counter bytes per launch; two launches per call move 5 A by construction (forward: "
-                                        "read x, write out; reverse: read x, read + rewrite out) against SURVEY §8(d)'s 2 A for the stage")
-            if "rocprof_avg_launch_us" in tj_dom:
-                # the committed rocprofv3 --kernel-trace --stats summary times the same launch with every dispatch separated by
-                # the tracer (and at its own clocks): ~10 % longer than the HIP-event figure of back-to-back launches above.
-                # Both are stated; `frac` is the HIP-event one.
-                rp = tj_dom["rocprof_avg_launch_us"] * 1e-3
-                roof["rocprof_avg_launch_ms"] = rp
-                roof["frac_at_rocprof_duration"] = roof["frac"] * roof["avg_launch_ms"] / rp
-                roof["duration_note"] = ("avg_launch_ms: HIP events on the launch stream, launches back to back (this run); "
-                                         "rocprof_avg_launch_ms: profiles/*kernel_stats.csv of the committed profile, dispatches separated by the tracer")
-        roof["limited_by"] = limited_by(power, roof)
         out = {
             "metric": "frames_per_sec (5 s 16 kHz binaural clips, 625 STFT frames each, offline forward)",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1159,63 +1166,123 @@ def main():
             "whole_path": {"algorithmic_tflops": FLOPS_PER_CLIP * total_clips / elapsed / 1e12,
                            "algorithmic_hbm_gbs": (BYTES_PER_CLIP * B + WEIGHT_BYTES) * world * args.steps / elapsed / 1e9,
                            "frac_hbm_peak": (BYTES_PER_CLIP * B + WEIGHT_BYTES) * world * args.steps / elapsed / 1e9 / (PEAK_HBM_GBS * world)},
-            "roofline": roof,
-            "power": power,
-            "n_ranks_seen": ranks_seen, "allreduce_32B_us": allreduce_us,
+            "n_ranks_seen": ranks_seen,
             "range_check": {"mode": "deferred" if net.range_check is True else net.range_check, "flag_raised": range_flag_raised},
-            # ms per step of each C-ABI call: the dominant one live over the timed region, the rest from the instrumented
-            # warm-up step
-            "kernels_ms_per_step": {k: v["avg_ms"] * breakdown[k]["launches"]
-                                    for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["avg_ms"] * breakdown[kv[0]]["launches"])},
             "metric_sums": [float(v) for v in sums.tolist()],
         }
-        emb_rows, kept = None, {}
-        if not args.no_secondary and world == 1 and args.batch == 32 and not args.gemm:
-            out["secondary"] = secondary_measurements(net, dev, mix[:8], emb[:8])
-            emb_rows = out["secondary"].pop("_embed_b64_rows", None)
-            kept = {k: out["secondary"].pop(k) for k in [k for k in out["secondary"] if k.startswith("_y_")]}
-        out["parity"] = None
-        if not args.no_cpu_baseline and world == 1:
-            import tempfile
-            with tempfile.TemporaryDirectory() as tmp:
-                dump = os.path.join(tmp, "cpu_leg.npz")
-                out["cpu_baseline"] = cpu_baseline_subprocess(dump=dump)
-                emb_cpu = out["cpu_baseline"].pop("embed_cpu_baseline", None)
-                if os.path.exists(dump):
-                    # parity inside the driver-run line: HIP vs the reference outputs the cpu leg just produced
-                    try:
-                        out["parity"], ref = parity_object(net, dev, dump)
-                        log(f"parity: {out['parity']}")
-                        if "secondary" in out:
-                            secondary_parity(out["secondary"], kept, ref)
-                            log("secondary parity: " + json.dumps({k: v.get("parity") for k, v in out["secondary"].items()
-                                                                   if isinstance(v, dict) and "parity" in v}))
-                        sec = out.get("secondary", {}).get("embed_b64")
-                        if isinstance(sec, dict) and emb_rows is not None and "emb" in ref.files:
-                            er = torch.from_numpy(ref["emb"]).double()
-                            eh = emb_rows[:er.shape[0]].double()
-                            cos = torch.nn.functional.cosine_similarity(eh, er, dim=-1)
-                            sec["embedding_cos_min"] = float(cos.min())
-                            sec["embedding_max_abs"] = float((eh - er).abs().max())
-                            sec["parity_clips"] = int(er.shape[0])
-                            sec["parity_against"] = ("oracle/embedder_oracle.py fp32 on the full-length enrollment(s) of the first row(s) "
-                                                     "(one 5 s clip costs the CPU ~10^4 x the GPU's time; trunk restated from espnet2: "
-                                                     "parity unpinned, DESIGN.md §2)")
-                            sec["cpu_baseline"] = emb_cpu
-                    except Exception as e:
-                        out["parity"] = {"error": repr(e)[:300]}
-        else:
-            out["cpu_baseline"] = None
-        # context only: the reference's op sequence on this GPU's libraries (never `vs_baseline`: BASELINE.md holds no
-        # published number for this metric, so that field stays null by contract)
-        out["gpu_library_baseline"] = None
-        if world == 1 and not args.no_gpu_library_baseline and not args.no_cpu_baseline:
-            net._ws.clear()
-            torch.cuda.empty_cache()
-            g = gpu_library_baseline_subprocess()
-            out["gpu_library_baseline"] = g
-            if g.get("value"):
-                out["vs_gpu_library_baseline"] = value / g["value"]
+        if args.full:
+            w = KERNEL_WORK[dom]
+            traffic, traffic_src, tj_dom = None, None, None
+            tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")     # HBM bytes per launch from the PMC passes
+            if os.path.exists(tfile):
+                tj = json.load(open(tfile))
+                if tj.get("batch_per_gpu") == B and dom in tj.get("kernels", {}):
+                    tj_dom = tj["kernels"][dom]
+                    traffic = tj["kernels"][dom]["hbm_bytes_per_launch"]    # per kernel launch (rocprofv3 dispatch)
+                    traffic_src = ("profiles/pmc_traffic.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                   "bench, committed with the kernels; source profile: %s) — not re-measured in this run"
+                                   % tj.get("source", "see profiles/README.md"))
+            if w["bound"] == "mfma":
+                ach = w["flops"] * B / (kern[dom]["avg_ms"] * 1e-3) / 1e12
+                peak = PEAK_F16_MFMA_TFLOPS if net.gemm_mode == "f16x3" else PEAK_FP32_MFMA_TFLOPS
+                roof = dict(kernel=dom, bound="mfma", achieved=ach, peak=peak, unit="TFLOP/s", frac=ach / peak,
+                            traffic=traffic,
+                            note=("algorithmic fp32-equivalent FLOPs; f16x3 mode executes 3x as many fp16 MFMA FLOPs, "
+                                  "peak = dense fp16 MFMA") if net.gemm_mode == "f16x3" else "exact fp32 MFMA")
+            else:
+                ach = w["bytes"] * B / (kern[dom]["avg_ms"] * 1e-3) / 1e9
+                roof = dict(kernel=dom, bound="hbm", achieved=ach, peak=PEAK_HBM_GBS, unit="GB/s",
+                            frac=ach / PEAK_HBM_GBS, traffic=traffic)
+            lpc = LAUNCHES_PER_CALL.get(dom, 1)
+            roof["traffic_source"] = traffic_src
+            roof["kernel_function"] = KERNEL_NAME.get(dom, dom)
+            roof["launches_per_call"] = lpc            # achieved = work of one call / duration of one call (= per launch too)
+            roof["avg_call_ms"] = kern[dom]["avg_ms"]
+            roof["event_samples"] = roof_samples       # calls of the dominant entry point bracketed with HIP events in the timed region
+            roof["avg_launch_ms"] = kern[dom]["avg_ms"] / lpc
+            # the same call in the fully instrumented warm-up step (event pairs around every call, as rocprofv3's tracer
+            # also separates the dispatches): the figure to hold against profiles/*kernel_stats*.csv
+            roof["avg_launch_ms_instrumented_step"] = breakdown[dom]["avg_ms"] / lpc
+            roof["share_of_gpu_time"] = kern[dom]["avg_ms"] * breakdown[dom]["launches"] / gpu_ms
+            # the same kernel against the other roofline, and against what the chip sustains under its 1400 W package limit
+            roof["frac_hbm"] = w["bytes"] * B / (kern[dom]["avg_ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS
+            if w["bound"] == "mfma" and net.gemm_mode == "f16x3":
+                roof["executed_fp16_tflops"] = 3.0 * roof["achieved"]
+                roof["frac_of_measured_mfma_rate_at_power_cap"] = 3.0 * roof["achieved"] / MEASURED_MFMA16_TFLOPS_AT_CAP
+            if tj_dom is not None:
+                for k_ in ("mfma_busy", "valu_busy"):
+                    if k_ in tj_dom:
+                        roof[k_] = tj_dom[k_]
+                if "ratio_to_survey_8d_per_call" in tj_dom:     # the contract's byte count for the stage (2 A), next to the kernel's own
+                    roof["traffic_ratio_to_survey_8d_stage_bytes"] = tj_dom["ratio_to_survey_8d_per_call"]
+                    roof["traffic_note"] = ("traffic = counter bytes per launch; two launches per call move 5 A by construction (forward: "
+                                            "read x, write out; reverse: read x, read + rewrite out) against SURVEY §8(d)'s 2 A for the stage")
+                if "rocprof_avg_launch_us" in tj_dom:
+                    # the committed rocprofv3 --kernel-trace --stats summary times the same launch with every dispatch separated by
+                    # the tracer (and at its own clocks): ~10 % longer than the HIP-event figure of back-to-back launches above.
+                    # Both are stated; `frac` is the HIP-event one.
+                    rp = tj_dom["rocprof_avg_launch_us"] * 1e-3
+                    roof["rocprof_avg_launch_ms"] = rp
+                    roof["frac_at_rocprof_duration"] = roof["frac"] * roof["avg_launch_ms"] / rp
+                    roof["duration_note"] = ("avg_launch_ms: HIP events on the launch stream, launches back to back (this run); "
+                                             "rocprof_avg_launch_ms: profiles/*kernel_stats.csv of the committed profile, dispatches separated by the tracer")
+            roof["limited_by"] = limited_by(power, roof)
+            out.update({
+                "roofline": roof,
+                "power": power,
+                "allreduce_32B_us": allreduce_us,
+                # ms per step of each C-ABI call: the dominant one live over the timed region, the rest from the instrumented
+                # warm-up step
+                "kernels_ms_per_step": {k: v["avg_ms"] * breakdown[k]["launches"]
+                                        for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["avg_ms"] * breakdown[kv[0]]["launches"])},
+            })
+            emb_rows, kept = None, {}
+            if not args.no_secondary and world == 1 and args.batch == 32 and not args.gemm:
+                out["secondary"] = secondary_measurements(net, dev, mix[:8], emb[:8])
+                emb_rows = out["secondary"].pop("_embed_b64_rows", None)
+                kept = {k: out["secondary"].pop(k) for k in [k for k in out["secondary"] if k.startswith("_y_")]}
+            out["parity"] = None
+            if not args.no_cpu_baseline and world == 1:
+                import tempfile
+                with tempfile.TemporaryDirectory() as tmp:
+                    dump = os.path.join(tmp, "cpu_leg.npz")
+                    out["cpu_baseline"] = cpu_baseline_subprocess(dump=dump)
+                    emb_cpu = out["cpu_baseline"].pop("embed_cpu_baseline", None)
+                    if os.path.exists(dump):
+                        # parity inside the driver-run line: HIP vs the reference outputs the cpu leg just produced
+                        try:
+                            out["parity"], ref = parity_object(net, dev, dump)
+                            log(f"parity: {out['parity']}")
+                            if "secondary" in out:
+                                secondary_parity(out["secondary"], kept, ref)
+                                log("secondary parity: " + json.dumps({k: v.get("parity") for k, v in out["secondary"].items()
+                                                                       if isinstance(v, dict) and "parity" in v}))
+                            sec = out.get("secondary", {}).get("embed_b64")
+                            if isinstance(sec, dict) and emb_rows is not None and "emb" in ref.files:
+                                er = torch.from_numpy(ref["emb"]).double()
+                                eh = emb_rows[:er.shape[0]].double()
+                                cos = torch.nn.functional.cosine_similarity(eh, er, dim=-1)
+                                sec["embedding_cos_min"] = float(cos.min())
+                                sec["embedding_max_abs"] = float((eh - er).abs().max())
+                                sec["parity_clips"] = int(er.shape[0])
+                                sec["parity_against"] = ("oracle/embedder_oracle.py fp32 on the full-length enrollment(s) of the first row(s) "
+                                                         "(one 5 s clip costs the CPU ~10^4 x the GPU's time; trunk restated from espnet2: "
+                                                         "parity unpinned, DESIGN.md §2)")
+                                sec["cpu_baseline"] = emb_cpu
+                        except Exception as e:
+                            out["parity"] = {"error": repr(e)[:300]}
+            else:
+                out["cpu_baseline"] = None
+            # context only: the reference's op sequence on this GPU's libraries (never `vs_baseline`: BASELINE.md holds no
+            # published number for this metric, so that field stays null by contract)
+            out["gpu_library_baseline"] = None
+            if world == 1 and not args.no_gpu_library_baseline and not args.no_cpu_baseline:
+                net._ws.clear()
+                torch.cuda.empty_cache()
+                g = gpu_library_baseline_subprocess()
+                out["gpu_library_baseline"] = g
+                if g.get("value"):
+                    out["vs_gpu_library_baseline"] = value / g["value"]
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -1,5 +1,5 @@
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lookoncetohear_amd import synth, config
 from lookoncetohear_amd.net import Net
 from oracle import tfgridnet_oracle as O

@@ -13,7 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(n, plain=False):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--dry-run-cpu"]
+    # --full: the line then carries the exchange step by itself (`allreduce_32B_us`) too
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--dry-run-cpu",
+           "--full"]
     if n > 1 and not plain:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
                "127.0.0.1", "--master-port", "29541"] + cmd[1:]
@@ -44,7 +46,7 @@ def test_bench_plumbing_world2_gloo():
 
 def test_bench_plain_launch_starts_its_own_ranks():
     """`python bench.py --gpus 2 --dry-run-cpu` with NO launcher around it (the shape of the driver's N = 1 command with N
-    changed; VERDICT r5 weak 3: this died with `AssertionError: --gpus 2 but WORLD_SIZE=1`): bench.py re-executes itself
+    changed; VERDICT r5 weak 3: this died with `AssertionError: --gpus 2 but WORLD_SIZE=1`): bench.py runs itself
     under torch.distributed.run and rank 0 prints the same single line as the externally launched form."""
     two = _run(2, plain=True)
     assert two["n_gpus"] == 2 and two["n_ranks_seen"] == 2 and two["metric_sums"][3] == 4.0 and two["dry_run"]
