@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header (15); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -443,6 +443,28 @@ int lh_render_binaural(const float* src, const float* rir, const float* gain, co
 int lh_metric_sums(const float* outputs, const float* target, const float* mixture, const float* emb,
                    const float* emb_gt, double* scratch, float* rows, double* sums, int B, int n_samples,
                    int emb_dim, lh_stream_t stream);
+
+/* Binaural cue errors on the device (ABI 15; reference src/eval/binaural.py: itd_diff, ild_diff, chunk_and_mask): per utterance
+ * the change of the interaural time and level differences between the estimate and the target, from direct fp64 sums.
+ *   est, gt   [B][2][n_samples] (channel 0 = left, 1 = right); sr = sample rate
+ *   frame     0: static mode, one segment = the whole clip; > 0: moving mode, segments of `frame` samples (the reference's
+ *             round(0.25 sr)), the last one zero-padded, counted when max over channels of sqrt(mean(gt^2)) over the frame
+ *             is >= rms_threshold (ignored in static mode)
+ *   per segment: ILD = 10 log10(sum L^2 / sum R^2); tau = argmax |cc[tau]| over tau = -t .. t (first maximum wins) of the
+ *             circular cross-correlation cc[tau] = sum_n L[(n + tau) mod len] R[n], t = min(round(1e-3 sr), len / 2);
+ *             ITD = tau / sr * 1e6 us
+ *   scratch   fp64 workspace, B*C*(T*72 + 8) doubles, with len = (frame ? frame : n_samples), C = (frame ? ceil(n_samples /
+ *             frame) : 1) segments and T = ceil(len / 4096) tiles per segment; its tail [B][C][8] holds the segment records
+ *             (tau_est, tau_gt, ild_est, ild_gt, itd_est, itd_gt, counted, 0)
+ *   rows      [B][2] fp64 = (delta_itd_us, delta_ild_db): static |ITD_est - ITD_gt|, |ILD_est - ILD_gt|; moving: the mean over
+ *             counted segments of |ITD_est - ITD_gt|, and |mean ILD_est - mean ILD_gt|; NaN when no segment counts
+ *   sums      [4] fp64 = (sum delta_itd over finite rows, count, sum delta_ild over finite rows, count)
+ * LH_ERR_UNSUPPORTED unless 1 <= round(1e-3 sr) <= 16 (ties to even: sr 500 .. 16500), for an odd n_samples in static mode
+ * and for an odd frame.  No atomics:
+ * bit-identical from run to run, and row b does not depend on the other utterances of the batch.
+ */
+int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B, int n_samples,
+                     int sr, int frame, double rms_threshold, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

@@ -7,11 +7,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_int, c_void_p
+from ctypes import c_double, c_int, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -51,6 +51,7 @@ SIGNATURES = {
     "lh_emb_head": [_P] * 7 + [_I, _I, _P],
     "lh_render_binaural": [_P] * 8 + [_I, _I, _I, _I, _P],
     "lh_metric_sums": [_P] * 8 + [_I, _I, _I, _P],
+    "lh_binaural_cues": [_P] * 5 + [_I, _I, _I, _I, c_double, _P],
     "lh_range_status": [_P, _P],
     "lh_range_flag_copy": [_P, _P, _P],
     "lh_range_flag_clear": [_P, _P],

@@ -136,6 +136,166 @@ __global__ void __launch_bounds__(64) k_metric_total(const double* __restrict__ 
     }
 }
 
+
+// ---- binaural cue errors (reference src/eval/binaural.py: itd_diff, ild_diff, chunk_and_mask) ------------------------------
+// Per segment and signal (est, gt): the circular cross-correlation cc[tau] = sum_m L[(m + tau) mod len] R[m] over the lags
+// -BC_TMAX..BC_TMAX and the channel energies, as DIRECT fp64 sums (the reference goes through rfft / irfft; a product of two
+// fp32 samples is exact in fp64, so every term is exact and only the additions round).  A segment is the whole clip (static
+// mode) or a frame of `frame` samples, the last one zero-padded (moving mode).
+//   k_bc_tiles     grid (tiles, segments, B): one workgroup per BC_TILE positions of a segment.  Lane l owns the BC_RUN
+//                  positions m0 = tile * BC_TILE + l * BC_RUN ..; it reads its BC_RUN right samples once and a window of
+//                  BC_RUN + 2 BC_TMAX left samples (the halo read modulo the segment length), then every (sample, lag) pair
+//                  is one fp64 FMA on registers.  Partials: [B][C][tiles][est, gt][BC_NV] (lags, sum L^2, sum R^2, 0).
+//   k_bc_segments  grid (segments, B): adds the tile partials in tile order; argmax |cc| (first maximum wins, as np.argmax),
+//                  ILD, ITD and the gt-RMS mask of the segment -> record [B][C][BC_REC].
+//   k_bc_rows      one wave per utterance: the counted segments' aggregate (mean |dITD|, |mean ILD_est - mean ILD_gt|).
+//   k_bc_total     the all-reduce payload: sums and counts of the finite rows, in utterance order.
+// Fixed reduction orders throughout and no atomics: bit-identical from run to run, and row b depends on utterance b only.
+constexpr int BC_TMAX = 16;                       // largest supported round(1e-3 sr): sr <= 16499
+constexpr int BC_LAGS = 2 * BC_TMAX + 1;
+constexpr int BC_RUN = 16;                        // positions per lane
+constexpr int BC_TILE = 256 * BC_RUN;
+constexpr int BC_NV = BC_LAGS + 3;                // lags, sum L^2, sum R^2, pad
+constexpr int BC_REC = 8;                         // tau_est, tau_gt, ild_est, ild_gt, itd_est, itd_gt, counted, 0
+
+__device__ __forceinline__ int bc_wrap(int p, int len) {
+    p %= len;
+    return p < 0 ? p + len : p;
+}
+
+// grid (tiles, C, B), block 256
+__global__ void __launch_bounds__(256) k_bc_tiles(const float* __restrict__ est, const float* __restrict__ gt,
+                                                  double* __restrict__ part, int n, int seglen) {
+    __shared__ double red[4][2 * BC_NV];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(tid);
+    const int t = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int seg0 = c * seglen;
+    const int valid = min(seglen, n - seg0);                  // positions >= valid are the zero padding of the last frame
+    const int tend = min(seglen, (t + 1) * BC_TILE);
+    const int m0 = t * BC_TILE + tid * BC_RUN;
+    for (int sig = 0; sig < 2; ++sig) {
+        const float* xl = (sig ? gt : est) + (long)b * 2 * n + seg0;
+        const float* xr = xl + n;
+        double acc[BC_LAGS + 2];
+#pragma unroll
+        for (int k = 0; k < BC_LAGS + 2; ++k) acc[k] = 0.0;
+        if (m0 < tend) {
+            float l[BC_RUN + 2 * BC_TMAX];
+            double r[BC_RUN];
+            if (m0 >= BC_TMAX && m0 + BC_RUN + BC_TMAX <= valid) {        // interior: no wrap, no padding, whole run
+#pragma unroll
+                for (int k = 0; k < BC_RUN + 2 * BC_TMAX; ++k) l[k] = xl[m0 - BC_TMAX + k];
+#pragma unroll
+                for (int j = 0; j < BC_RUN; ++j) r[j] = xr[m0 + j];
+            } else {                                                      // circular halo, padding, end of the segment
+#pragma unroll
+                for (int k = 0; k < BC_RUN + 2 * BC_TMAX; ++k) {
+                    const int p = bc_wrap(m0 - BC_TMAX + k, seglen);
+                    l[k] = p < valid ? xl[p] : 0.f;
+                }
+#pragma unroll
+                for (int j = 0; j < BC_RUN; ++j) r[j] = (m0 + j < tend && m0 + j < valid) ? xr[m0 + j] : 0.f;
+            }
+            // left sample q meets right sample j at lag q - j - BC_TMAX: each left value is widened once and used while it is
+            // live (acc[k] still takes its terms in increasing j)
+#pragma unroll
+            for (int q = 0; q < BC_RUN + 2 * BC_TMAX; ++q) {
+                const double lq = l[q];
+                if (q >= BC_TMAX && q < BC_TMAX + BC_RUN && m0 + q - BC_TMAX < tend) acc[BC_LAGS] = fma(lq, lq, acc[BC_LAGS]);
+#pragma unroll
+                for (int j = q > 2 * BC_TMAX ? q - 2 * BC_TMAX : 0; j <= (q < BC_RUN - 1 ? q : BC_RUN - 1); ++j)
+                    acc[q - j] = fma(lq, r[j], acc[q - j]);
+            }
+#pragma unroll
+            for (int j = 0; j < BC_RUN; ++j) acc[BC_LAGS + 1] = fma(r[j], r[j], acc[BC_LAGS + 1]);
+        }
+#pragma unroll
+        for (int k = 0; k < BC_LAGS + 2; ++k) {
+            const double v = wave_sum_f64(acc[k]);
+            if (lane == 0) red[wave][sig * BC_NV + k] = v;
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * BC_NV) {
+        const int k = tid % BC_NV;
+        const double v = k < BC_LAGS + 2 ? ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid] : 0.0;
+        part[(((long)b * gridDim.y + c) * gridDim.x + t) * 2 * BC_NV + tid] = v;
+    }
+}
+
+// grid (C, B), block 128
+__global__ void __launch_bounds__(128) k_bc_segments(const double* __restrict__ part, double* __restrict__ rec, int tiles,
+                                                     int tmax, int sr, int frame, double rms_threshold) {
+    __shared__ double sv[2 * BC_NV];
+    const int tid = threadIdx.x, c = blockIdx.x, b = blockIdx.y, C = gridDim.x;
+    const double* p = part + ((long)b * C + c) * tiles * 2 * BC_NV;
+    if (tid < 2 * BC_NV) {
+        double v = 0.0;
+        for (int t = 0; t < tiles; ++t) v += p[(long)t * 2 * BC_NV + tid];          // tile order
+        sv[tid] = v;
+    }
+    __syncthreads();
+    double* r = rec + ((long)b * C + c) * BC_REC;
+    if (tid < 2) {
+        const double* s = sv + tid * BC_NV;
+        int arg = BC_TMAX - tmax;                                 // tau = -tmax .. tmax in that order, first maximum wins
+        double best = fabs(s[arg]);
+        for (int k = arg + 1; k <= BC_TMAX + tmax; ++k) {
+            const double a = fabs(s[k]);
+            if (best == best && (a != a || a > best)) { best = a; arg = k; }    // np.argmax: the first NaN is the maximum
+        }
+        const double tau = (double)(arg - BC_TMAX);
+        r[tid] = tau;
+        r[2 + tid] = 10.0 * log10(s[BC_LAGS] / s[BC_LAGS + 1]);
+        r[4 + tid] = tau / (double)sr * 1e6;
+    } else if (tid == 2) {
+        double counted = 1.0;                                     // static mode: every clip counts
+        if (frame > 0) {                                          // max over channels of the gt RMS (NaN propagates, as np.max)
+            const double a = sqrt(sv[BC_NV + BC_LAGS] / (double)frame), g = sqrt(sv[BC_NV + BC_LAGS + 1] / (double)frame);
+            const double m = (a != a || a >= g) ? a : g;
+            counted = m >= rms_threshold ? 1.0 : 0.0;
+        }
+        r[6] = counted;
+        r[7] = 0.0;
+    }
+}
+
+// rows [B][2] = (delta_itd_us, delta_ild_db).  One wave per utterance, four per workgroup, grid ceil(B / 4)
+__global__ void __launch_bounds__(256) k_bc_rows(const double* __restrict__ rec, double* __restrict__ rows, int B, int C) {
+    const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x * 4 + wave_id(tid);
+    if (b >= B) return;
+    double ditd = 0.0, cnt = 0.0, ild_e = 0.0, ild_g = 0.0;
+    for (int c = lane; c < C; c += 64) {
+        const double* r = rec + ((long)b * C + c) * BC_REC;
+        if (r[6] != 0.0) {
+            ditd += fabs(r[4] - r[5]);
+            cnt += 1.0;
+            ild_e += r[2];
+            ild_g += r[3];
+        }
+    }
+    ditd = wave_sum_f64(ditd); cnt = wave_sum_f64(cnt); ild_e = wave_sum_f64(ild_e); ild_g = wave_sum_f64(ild_g);
+    if (lane == 0) {
+        const double nan = __builtin_nan("");                     // np.mean of no counted segment
+        rows[b * 2 + 0] = cnt > 0.0 ? ditd / cnt : nan;
+        rows[b * 2 + 1] = cnt > 0.0 ? fabs(ild_e / cnt - ild_g / cnt) : nan;
+    }
+}
+
+// sums [4] = (sum delta_itd over finite rows, count, sum delta_ild over finite rows, count); lane k walks column k in order
+__global__ void __launch_bounds__(64) k_bc_total(const double* __restrict__ rows, double* __restrict__ sums, int B) {
+    const int k = threadIdx.x;
+    if (k < 2) {
+        double s = 0.0, cnt = 0.0;
+        for (int b = 0; b < B; ++b) {
+            const double v = rows[b * 2 + k];
+            if (v - v == 0.0) { s += v; cnt += 1.0; }              // finite: inf - inf and NaN - NaN are NaN
+        }
+        sums[2 * k] = s;
+        sums[2 * k + 1] = cnt;
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_metric_sums(const float* outputs, const float* target, const float* mixture, const float* emb,
@@ -150,5 +310,25 @@ extern "C" int lh_metric_sums(const float* outputs, const float* target, const f
     hipLaunchKernelGGL(k_metric_finish, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, scratch, emb, emb_gt, rows, B,
                        n_samples, emb_dim);
     hipLaunchKernelGGL(k_metric_total, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch, sums, B);
+    return check_launch();
+}
+
+extern "C" int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B,
+                                int n_samples, int sr, int frame, double rms_threshold, lh_stream_t stream) {
+    using namespace lh;
+    if (!est || !gt || !scratch || !rows || !sums || B <= 0 || n_samples <= 0 || sr <= 0 || frame < 0) return LH_ERR_ARG;
+    const int tmax = (int)rint(1e-3 * sr);                       // Python round(): ties to even
+    if (tmax < 1 || tmax > BC_TMAX || (frame == 0 && (n_samples & 1)) || (frame & 1)) return LH_ERR_UNSUPPORTED;
+    const int seglen = frame > 0 ? frame : n_samples;
+    const int C = frame > 0 ? (n_samples + frame - 1) / frame : 1;
+    const int tiles = (seglen + BC_TILE - 1) / BC_TILE;
+    const int te = min(tmax, seglen / 2);                         // compute_itd: t_max is capped at len // 2
+    double* part = scratch;
+    double* rec = scratch + (long)B * C * tiles * 2 * BC_NV;
+    hipLaunchKernelGGL(k_bc_tiles, dim3(tiles, C, B), dim3(256), 0, (hipStream_t)stream, est, gt, part, n_samples, seglen);
+    hipLaunchKernelGGL(k_bc_segments, dim3(C, B), dim3(128), 0, (hipStream_t)stream, part, rec, tiles, te, sr, frame,
+                       rms_threshold);
+    hipLaunchKernelGGL(k_bc_rows, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, rec, rows, B, C);
+    hipLaunchKernelGGL(k_bc_total, dim3(1), dim3(64), 0, (hipStream_t)stream, rows, sums, B);
     return check_launch();
 }
