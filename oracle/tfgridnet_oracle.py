@@ -291,31 +291,59 @@ def gridnet_block(cfg: Cfg, p: dict, pre: str, X, st: dict, fast_lstm=False, tap
         taps[pre + "Y2"] = Y2
 
     # 3. Q/K/V: pointwise Linear + PReLU, head split, joint LayerNorm over (f, e)
+    Q, K, V = qkv_proj_ln(cfg, p, pre, Y2)
+
+    # 4. history rings
+    Kx, Vx, st["K_buf"], st["V_buf"] = history_concat(cfg, st["K_buf"], st["V_buf"], K, V)
+
+    # 5. local attention over exactly L slots (frames t-L+1..t), NO mask: zero history rows take part
+    O = local_attention(cfg, Q, Kx, Vx)
+    if taps is not None:
+        taps[pre + "Q"], taps[pre + "K"], taps[pre + "V"], taps[pre + "O"] = Q, K, V, O
+
+    # 6. head merge, projection, joint LayerNorm over (f, c), residual
+    return concat_proj_ln_res(cfg, p, pre, O, Y2)
+
+
+def qkv_proj_ln(cfg: Cfg, p: dict, pre: str, Y2):
+    """Q/K/V of one block: pointwise Linear + PReLU, head split, joint LayerNorm over (f, d) per head.
+    Y2 [B,T,F,C] -> Q, K [B*nh, T, F*E], V [B*nh, T, F*Vd]."""
+    B, T, Fq, C = Y2.shape
+    nh = cfg.nh
+
     def proj(nm, d):
         y = _prelu(Y2 @ p[pre + f"attn_conv_{nm}.0.weight"].t() + p[pre + f"attn_conv_{nm}.0.bias"],
                    p[pre + f"attn_conv_{nm}.1.weight"])                       # [B,T,F,nh*d]
         y = y.reshape(B, T, Fq, nh, d).permute(0, 3, 1, 2, 4).reshape(B * nh, T, Fq * d)
         return _ln(y, p[pre + f"attn_conv_{nm}.3.norm.weight"], p[pre + f"attn_conv_{nm}.3.norm.bias"], cfg.eps)
 
-    Q, K, V = proj("Q", E), proj("K", E), proj("V", Vd)
+    return proj("Q", cfg.E), proj("K", cfg.E), proj("V", cfg.Vd)
 
-    # 4. history rings
-    Kx = torch.cat([st["K_buf"], K], 1)                                          # [B*nh, T+L-1, F*E]
-    Vx = torch.cat([st["V_buf"], V], 1)
-    st["K_buf"] = Kx[:, -(L - 1):].clone()
-    st["V_buf"] = Vx[:, -(L - 1):].clone()
 
-    # 5. local attention over exactly L slots (frames t-L+1..t), NO mask: zero history rows take part
-    scale = 1.0 / math.sqrt(Fq * E)
+def history_concat(cfg: Cfg, K_buf, V_buf, K, V):
+    """History rows + new rows: Kx, Vx [B*nh, T+L-1, .] and the next K_buf, V_buf (the last L-1 rows)."""
+    Kx = torch.cat([K_buf, K], 1)
+    Vx = torch.cat([V_buf, V], 1)
+    return Kx, Vx, Kx[:, -(cfg.L - 1):].clone(), Vx[:, -(cfg.L - 1):].clone()
+
+
+def local_attention(cfg: Cfg, Q, Kx, Vx):
+    """Softmax attention of query frame t over exactly L slots Kx / Vx rows t..t+L-1, no mask.
+    Q [B*nh, T, F*E], Kx [B*nh, >= T+L-1, F*E], Vx [B*nh, >= T+L-1, F*Vd] -> O [B*nh, T, F*Vd]."""
+    T, L = Q.shape[1], cfg.L
+    scale = 1.0 / math.sqrt(cfg.F * cfg.E)
     sc = torch.stack([(Q * Kx[:, j:j + T]).sum(-1) for j in range(L)], dim=-1) * scale   # [B*nh,T,L]
     pr = torch.softmax(sc, dim=-1)
-    O = torch.zeros_like(V)
+    O = torch.zeros(Q.shape[0], T, Vx.shape[-1], dtype=Vx.dtype, device=Vx.device)
     for j in range(L):
         O = O + pr[:, :, j:j + 1] * Vx[:, j:j + T]
-    if taps is not None:
-        taps[pre + "Q"], taps[pre + "K"], taps[pre + "V"], taps[pre + "O"] = Q, K, V, O
+    return O
 
-    # 6. head merge, projection, joint LayerNorm over (f, c), residual
+
+def concat_proj_ln_res(cfg: Cfg, p: dict, pre: str, O, Y2):
+    """Head merge, Linear + PReLU, joint LayerNorm over (f, c), residual.  O [B*nh, T, F*Vd], Y2 [B,T,F,C] -> [B,T,F,C]."""
+    B, T, Fq, C = Y2.shape
+    nh, Vd = cfg.nh, cfg.Vd
     Mg = O.reshape(B, nh, T, Fq, Vd).permute(0, 2, 3, 1, 4).reshape(B, T, Fq, nh * Vd)
     P = _prelu(Mg @ p[pre + "attn_concat_proj.0.weight"].t() + p[pre + "attn_concat_proj.0.bias"],
                p[pre + "attn_concat_proj.1.weight"]).reshape(B, T, Fq * C)
