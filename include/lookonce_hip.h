@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (15); bumped on any signature change. */
+/* ABI version of this header (16); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -465,6 +465,48 @@ int lh_metric_sums(const float* outputs, const float* target, const float* mixtu
  */
 int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B, int n_samples,
                      int sr, int frame, double rms_threshold, lh_stream_t stream);
+
+/* ---- streaming sessions (ABI 16) --------------------------------------------------------------------------------------------
+ * A batched streaming host serves S listener SLOTS in lock-step (one 8 ms chunk of every slot per step; slot = batch row of
+ * every streaming entry point above).  These two launches bracket the chunk's launch sequence — first and last node of a
+ * captured per-chunk graph — and let slots open, close and fail one at a time, on the device and without a host wait (the
+ * reference has no counterpart: its streaming loop, `Net.predict(chunk, embed, state, pad=False)`, serves one listener).
+ *   lh_span_t  one tensor of per-slot streaming state: slot s owns bytes [s * bytes, (s + 1) * bytes) from `base`; `base`
+ *              and `bytes` are multiples of 16 (the store width).  lh_session_begin takes EVERY state tensor of the chunk
+ *              loop (both ping-pong sets of conv / deconv / iSTFT tails and inter-LSTM h, c; every K / V ring: 4 ring rows
+ *              per slot), lh_session_end the (h, c) tensors the chunk has just WRITTEN.  The table is a HOST array of
+ *              n_spans <= LH_SESSION_MAX_SPANS entries: it is validated here and travels in the launch's own arguments (a
+ *              captured graph keeps it), so no entry point reads device memory or waits.
+ *   chunk_in   [S][2][192] the step's input as the clients sent it (never written);  chunk [S][2][192] what the separator
+ *              reads: the row of a live slot, zeros for every other slot
+ *   cmd        [2][S] words of LH_SESSION_* bits: row 0 posted by the host (one asynchronous copy ahead of the step), row 1
+ *              posted by lh_session_end for the next chunk — separate words, so the host's copy cannot erase a RESET the
+ *              device posted meanwhile.  lh_session_begin acts on row 0 | row 1; lh_session_end consumes both.
+ *              Bits 8..30 of a host word with LH_SESSION_OPEN: the opening's generation (non-zero)
+ *   active     [S] 0 = idle, else the generation of the slot's current opening
+ *   fault      [S] DEVICE-ACCESSIBLE words the host reads in place (pinned host memory, written with system-scope vector
+ *              stores like the range flag above): set to the generation of the opening the device closed
+ *   out        [S][2][128] the chunk's output (lh_deconv_istft with keep_nonfinite = 1 and no range flag: nothing is hidden
+ *              from lh_session_end)
+ * Per slot, with c = cmd[0][s] | cmd[1][s]:  open = c has OPEN ? 1 : c has CLOSE ? 0 : active[s] != 0;  bad_in = open and one
+ * of the 384 samples of chunk_in[s] is inf / NaN;  live = open and not bad_in.
+ *   lh_session_begin  (grid over slot x tile) writes chunk[s] and, when c has RESET or bad_in, zeroes the slot's slice of
+ *              every span with 16-byte stores: non-finite data never enters the separator kernels and a re-used slot keeps
+ *              nothing of its previous listener.  It writes no word, so the workgroups of a slot all decide alike; a slot
+ *              with nothing pending and finite input costs a few loads per wave.
+ *   lh_session_end    (one workgroup per slot, the only writer of the words) overflow = live and a non-finite value in out[s]
+ *              or in the slot's slice of a span (a true fp32 overflow from finite input);  active[s] = generation if live and
+ *              not overflow, else 0;  fault[s] = 0 when c has OPEN, then the generation when bad_in or overflow;
+ *              cmd[0][s] = 0, cmd[1][s] = overflow ? RESET : 0;  out[s] = 0 unless the slot is active now.
+ * LH_ERR_ARG: null pointer, S <= 0, n_spans outside [1, LH_SESSION_MAX_SPANS] (lh_session_end: LH_SESSION_MAX_END_SPANS, the
+ * (h, c) pairs of four blocks), a span with a null or unaligned base or a size that is 0 or not a multiple of 16.  Neither entry point allocates or synchronises. */
+typedef struct { void* base; unsigned long long bytes; } lh_span_t;
+enum { LH_SESSION_RESET = 1, LH_SESSION_OPEN = 2, LH_SESSION_CLOSE = 4, LH_SESSION_GEN_SHIFT = 8, LH_SESSION_MAX_SPANS = 32,
+       LH_SESSION_MAX_END_SPANS = 8 };
+int lh_session_begin(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk, const unsigned* cmd,
+                     const unsigned* active, int S, lh_stream_t stream);
+int lh_session_end(const lh_span_t* spans, int n_spans, const float* chunk_in, float* out, unsigned* cmd, unsigned* active,
+                   unsigned* fault, int S, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -33,6 +33,9 @@ SIGNATURES = {
     "lh_ring_pack": [_P] * 4 + [_I, _I, _P],
     "lh_ring_unpack": [_P] * 4 + [_I, _I, _P],
     "lh_ring_advance": [_P, _I, _P],
+    # streaming sessions (ABI 16): first / last node of a SessionStreamer's per-chunk graph
+    "lh_session_begin": [_P, _I, _P, _P, _P, _P, _I, _P],
+    "lh_session_end": [_P, _I, _P, _P, _P, _P, _P, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)
@@ -127,7 +130,7 @@ class HipHost:
     """Device plumbing of the host classes (`Net`, `EmbedTFGridNet`, `BinauralRenderer`): where the C-ABI library comes
     from, which HIP stream the launches go to, which device is current around them, and where a caller-owned flag word
     lives.  ROCm device tensors only — there is no CPU path.  (tests/hipemu subclasses the hosts and overrides exactly
-    these four methods to drive the same host code over the emulated library; the product classes carry no test hook.)"""
+    these methods to drive the same host code over the emulated library; the product classes carry no test hook.)"""
     _host_name = "this module"
 
     def _lib(self, t) -> "Lib":
@@ -148,8 +151,12 @@ class HipHost:
 
     def _flag_words(self, device):
         """Two zeroed 32-bit words in pinned host memory: device-accessible, and readable by the host without a copy."""
+        return self._host_words(2, device)
+
+    def _host_words(self, n, device):
+        """`n` zeroed 32-bit words in pinned host memory (see `_flag_words`; also the source of asynchronous copies)."""
         import torch
-        return torch.zeros(2, dtype=torch.int32).pin_memory()
+        return torch.zeros(n, dtype=torch.int32).pin_memory()
 
 
 def selftest_device(lib: "Lib", device_index: int) -> None:

@@ -215,6 +215,139 @@ __global__ void __launch_bounds__(IS_NT) k_inter_matvec(const float* __restrict_
     if (cell_lane) cN[(long)seq * H + unit] = c * ((cflags & 2) ? 1.0f : 1.0f / QS_K2);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Streaming sessions (include/lookonce_hip.h, ABI 16): the first and the last node of a batched streamer's per-chunk graph.
+// Slots (batch rows) open, close and fail one at a time while the chunk loop goes on in lock-step.  Plain streaming
+// kernels: a few word loads and the slot's 1.5 KB input row per wave to decide, 16-byte stores to zero a slot's state.
+// Who writes what: k_session_begin writes the gated input and the state it zeroes, never a word, so every workgroup of a
+// slot reaches the same decision from the same unmodified inputs; k_session_end (one workgroup per slot, after every other
+// kernel of the chunk) repeats that decision and is the only writer of cmd / active / fault.
+// ------------------------------------------------------------------------------------------------------
+struct SessSpans { lh_span_t s[LH_SESSION_MAX_SPANS]; int n; };     // travels in the kernel arguments
+constexpr int SS_NT = 256;
+constexpr int SS_IN4 = NMIC * NFFT / 4;        // 96 float4 per input row
+constexpr int SS_OUT4 = NSRC * HOP / 4;        // 64 float4 per output row
+static_assert(SS_IN4 == 64 + 32 && SS_OUT4 == 64, "one wave reads an input row in two loads; index masks below");
+
+__device__ __forceinline__ bool nonfinite4(const float4& v) {
+    const unsigned m = 0x7f800000u;                // exponent all ones: inf / NaN
+    return (__float_as_uint(v.x) & m) == m || (__float_as_uint(v.y) & m) == m || (__float_as_uint(v.z) & m) == m ||
+           (__float_as_uint(v.w) & m) == m;
+}
+__device__ __forceinline__ bool wave_any(bool p) {           // every lane of the wave calls it
+    int v = p ? 1 : 0;
+    v |= __shfl_xor(v, 32); v |= __shfl_xor(v, 16); v |= __shfl_xor(v, 8);
+    v |= __shfl_xor(v, 4);  v |= __shfl_xor(v, 2);  v |= __shfl_xor(v, 1);
+    return v != 0;
+}
+
+struct SessDecision { unsigned cmd, gen; bool bad_in, live; };      // gen: the opening's generation, 0 = idle
+struct SessLoads { unsigned host, dev, act; float4 x0, x1; };
+// Both kernels are latency: a handful of dependent memory round trips at ~1-2 us each is all they cost when nothing happens.
+// So everything a decision needs is REQUESTED AT ONCE and unconditionally — the three words and the wave's two float4 of the
+// slot's input row — and only then looked at.
+__device__ __forceinline__ SessLoads sess_load(const float* __restrict__ chunk_in, const unsigned* cmd, const unsigned* active,
+                                               int S, int s, int lane) {
+    SessLoads l;
+    const float4* in4 = reinterpret_cast<const float4*>(chunk_in + (long)s * NMIC * NFFT);
+    l.host = cmd[s];
+    l.dev = cmd[S + s];
+    l.act = active[s];
+    l.x0 = in4[lane];
+    l.x1 = in4[64 + (lane & (SS_IN4 - 64 - 1))];   // 32 more float4: the upper half-wave reads them again
+    return l;
+}
+// Wave-uniform, and the same in every wave of every workgroup of the chunk's two session kernels; every lane calls it.
+__device__ __forceinline__ SessDecision sess_decide(const SessLoads& l) {
+    SessDecision d;
+    d.cmd = l.host | l.dev;
+    d.gen = l.act;
+    if (d.cmd & LH_SESSION_OPEN) {
+        d.gen = (l.host >> LH_SESSION_GEN_SHIFT) & 0x7fffffu;
+        if (d.gen == 0) d.gen = 1;
+    } else if (d.cmd & LH_SESSION_CLOSE) {
+        d.gen = 0;
+    }
+    d.bad_in = wave_any(nonfinite4(l.x0) || nonfinite4(l.x1)) && d.gen != 0;      // an idle slot's input row is ignored
+    d.live = d.gen != 0 && !d.bad_in;
+    return d;
+}
+
+// grid (tiles, S), block 256
+__global__ void __launch_bounds__(SS_NT) k_session_begin(SessSpans sp, const float* __restrict__ chunk_in,
+                                                         float* __restrict__ chunk, const unsigned* __restrict__ cmd,
+                                                         const unsigned* __restrict__ active, int S) {
+    const int tid = threadIdx.x, s = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, tid & 63);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const long o = (long)s * SS_IN4 + min(tid, SS_IN4 - 1);
+    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[o];
+    const SessDecision d = sess_decide(l);
+    if (tile == 0 && tid < SS_IN4)                 // gate: only a live slot's samples reach the separator
+        reinterpret_cast<float4*>(chunk)[o] = d.live ? mine : z;
+    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
+    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the slot's slice of every state tensor
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        float4* p = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)s * sp.s[i].bytes);
+        const long hi = n16 * (tile + 1) / ntile;
+        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) p[j] = z;
+    }
+}
+
+// grid S, block 1024.  One workgroup per slot scans the slot's output row and fresh (h, c): 150 KB.  Every thread requests its
+// share of up to SE_SP spans in one go (SE_U float4 per span: 2048 cover a 97 x 64 state row) before it looks at any of them —
+// a loop that waited for each load took 26 us per chunk (profiles/r08a_sessions_cost.txt).
+constexpr int SE_NT = 1024, SE_SP = LH_SESSION_MAX_END_SPANS, SE_U = 2;
+__global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, const float* __restrict__ chunk_in, float* out,
+                                                       unsigned* cmd, unsigned* active, unsigned* fault, int S) {
+    __shared__ int wbad[SE_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, s = blockIdx.x;
+    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, lane);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4* o4 = reinterpret_cast<float4*>(out) + (long)s * SS_OUT4;
+    const float4 ov = o4[tid & (SS_OUT4 - 1)];
+    // branch-free: a span the table does not have is span 0 again, an index past the end is the last one (re-reading is free)
+    float4 v[SE_SP][SE_U];
+#pragma unroll
+    for (int i = 0; i < SE_SP; ++i) {
+        const lh_span_t sq = sp.s[i < sp.n ? i : 0];
+        const int last = (int)min((long)(sq.bytes >> 4), (long)SE_U * SE_NT) - 1;
+        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)s * sq.bytes);
+#pragma unroll
+        for (int u = 0; u < SE_U; ++u) v[i][u] = p[min(tid + u * SE_NT, last)];
+    }
+    bool bad = nonfinite4(ov);
+#pragma unroll
+    for (int i = 0; i < SE_SP; ++i)
+#pragma unroll
+        for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
+    for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
+                                                          (unsigned long long)s * sp.s[i].bytes);
+        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(p[j]);
+    }
+    const SessDecision d = sess_decide(l);
+    bad = wave_any(bad);
+    if (lane == 0) wbad[tid >> 6] = bad ? 1 : 0;
+    __syncthreads();                               // also: every wave has read the words thread 0 is about to write
+    int any = 0;
+#pragma unroll
+    for (int w = 0; w < SE_NT / 64; ++w) any |= wbad[w];
+    // a true fp32 overflow from finite input: non-finite output or fresh (h, c) of a live slot
+    const bool overflow = d.live && any != 0;
+    const bool on = d.live && !overflow;
+    if (!on && tid < SS_OUT4) o4[tid] = z;
+    if (tid == 0) {
+        active[s] = on ? d.gen : 0u;
+        // pinned host memory the host reads in place: plain stores at system scope, like the range flag (lh_backend.hip)
+        if (d.bad_in || overflow) __hip_atomic_store(&fault[s], d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[s], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        cmd[s] = 0u;
+        cmd[S + s] = overflow ? (unsigned)LH_SESSION_RESET : 0u;
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -242,4 +375,42 @@ extern "C" int lh_inter_matvec(const float* x, const void* wih_pk, const float* 
                                const float* blin, const float* h0, const float* c0, float* hN, float* cN, float* out,
                                int B, int T, lh_stream_t stream) {
     return lh_inter_matvec_win(x, wih_pk, b_sum, whh, wlin_pk, blin, h0, c0, hN, cN, out, B, T, 0, T, 0, stream);
+}
+
+namespace lh {
+static bool sess_spans(const lh_span_t* spans, int n_spans, SessSpans& sp) {
+    if (!spans || n_spans < 1 || n_spans > LH_SESSION_MAX_SPANS) return false;
+    sp = SessSpans{};
+    for (int i = 0; i < n_spans; ++i) {
+        if (!spans[i].base || ((unsigned long long)(size_t)spans[i].base & 15) || !spans[i].bytes || (spans[i].bytes & 15))
+            return false;
+        sp.s[i] = spans[i];
+    }
+    sp.n = n_spans;
+    return true;
+}
+}  // namespace lh
+
+extern "C" int lh_session_begin(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk, const unsigned* cmd,
+                                const unsigned* active, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || S <= 0 || !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    // ~10 MB of state per slot, mostly rings: enough tiles that one RESET is microseconds (64 workgroups zero a slot in ~13 us),
+    // few enough that the idle launch of a large batch stays a handful of early-out workgroups per CU
+    const int tiles = S <= 16 ? 64 : (S >= 64 ? 16 : 1024 / S);
+    hipLaunchKernelGGL(k_session_begin, dim3(tiles, S), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in, chunk, cmd, active,
+                       S);
+    return check_launch();
+}
+
+extern "C" int lh_session_end(const lh_span_t* spans, int n_spans, const float* chunk_in, float* out, unsigned* cmd,
+                              unsigned* active, unsigned* fault, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!chunk_in || !out || !cmd || !active || !fault || S <= 0 || n_spans > SE_SP || !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_end, dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, chunk_in, out, cmd, active, fault, S);
+    return check_launch();
 }

@@ -21,6 +21,7 @@ path raises if the HIP library is missing or the tensors are not on the GPU).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from typing import Dict, Optional, Tuple
@@ -297,6 +298,10 @@ class Net(_cabi.HipHost, nn.Module):
     def make_streamer(self, batch_size: int, device, use_graph: bool = True):
         """Chunked real-time front end (BASELINE configs[1]): see `Streamer`."""
         return Streamer(self, batch_size, device, use_graph)
+
+    def make_session_streamer(self, n_slots: int, device, use_graph: bool = True):
+        """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`."""
+        return SessionStreamer(self, n_slots, device, use_graph)
 
     # ------------------------------------------------------------------------------------------------
     # host-side plumbing
@@ -823,11 +828,14 @@ class Net(_cabi.HipHost, nn.Module):
             lib.call("lh_embed_proj_ln", P(embed), P(pk["emb_w"]), P(pk["emb_b"]), P(pk["emb_ln_w"]), P(pk["emb_ln_b"]),
                      P(gain_raw), P(gain), embed.shape[0], st)
 
-    def _stream_chunk(self, x, gain, sin: dict, sout: dict, rings, pos, y, pk: dict, ws: dict, flag=None):
+    def _stream_chunk(self, x, gain, sin: dict, sout: dict, rings, pos, y, pk: dict, ws: dict, flag=None,
+                      keep_nonfinite: int = 0):
         """One chunk of ONE frame for `Streamer`: the launches of `_separate` with every state tensor read from `sin` and
         written to `sout` (preallocated), the K / V history in per-block persistent rings, the speaker gain given.
         `pk` / `ws`: the packed weights and the T=1 workspace, OWNED by the caller — a captured graph holds raw pointers
-        into them, so they must not be the entries `_weights` / `_workspace` may replace or evict later."""
+        into them, so they must not be the entries `_weights` / `_workspace` may replace or evict later.
+        `keep_nonfinite`: lh_deconv_istft's switch — 0 for `Streamer` (silence, not NaN, reaches a listener), 1 for
+        `SessionStreamer`, whose own last kernel looks at the samples and silences the slot."""
         lib = self._lib(x)
         dev = x.device
         hop, nfft = self.stft_chunk_size, self.nfft
@@ -858,7 +866,7 @@ class Net(_cabi.HipHost, nn.Module):
                      P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(g) if g is not None else None, P(xa), Bn, T, st)
         lib.call("lh_deconv_istft", P(xa), P(sin["deconv_buf"]), P(sout["deconv_buf"]), P(sin["istft_buf"]),
                  P(sout["istft_buf"]), P(pk["deconv_w"]), P(pk["deconv_b"]), P(pk["wfb_dec"]), P(y),
-                 P(flag) if flag is not None else None, 0, Bn, T, st)
+                 P(flag) if flag is not None else None, keep_nonfinite, Bn, T, st)
 
 
 
@@ -924,20 +932,26 @@ class Streamer:
             self._ws = net._workspace(B, 1, dev)
             net._ws.pop((B, 1, str(dev)), None)          # private to this streamer from now on
         if use_graph:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for k in (0, 1):                # warm-up: packs weights, allocates the T=1 workspace
-                    self._body(k)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graphs = []
-            for k in (0, 1):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._body(k)
-                self.graphs.append(g)
+            self.graphs = self._capture(self._body, dev)
             self.graph = self.graphs[0]
             self.reset()
+
+    @staticmethod
+    def _capture(body, dev) -> list:
+        """The two alternating per-chunk graphs of `body(k)`, k = 0, 1 (after one eager pass of each on a side stream)."""
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for k in (0, 1):                    # warm-up: packs weights, allocates the T=1 workspace
+                body(k)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graphs = []
+        for k in (0, 1):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                body(k)
+            graphs.append(g)
+        return graphs
 
     def _body(self, k: int):
         with self.net._device_ctx(self.chunk):
@@ -966,6 +980,22 @@ class Streamer:
 
     def step(self, chunk: torch.Tensor) -> torch.Tensor:
         """chunk [B, 2, 192] (128 new + 64 look-ahead samples) -> [B, 2, 128]."""
+        self._check_repacked()
+        if self.net.range_check and int(self.range_flag[0]) != 0:     # host read of the pinned word: free
+            self.range_flag.zero_()
+            raise RuntimeError("LH_ERR_RANGE: an earlier chunk produced non-finite samples, emitted as zeros (inf / NaN in "
+                               "the input or in the carried state); reset() the streamer")
+        self._check_versions()
+        self.chunk.copy_(chunk)
+        with torch.no_grad():
+            if self.graphs is not None:
+                self.graphs[self.parity].replay()
+            else:
+                self._body(self.parity)
+        self.parity ^= 1
+        return self.out
+
+    def _check_repacked(self):
         # O(1) staleness check (re-deriving the pack key walks all 130 parameters: ~0.1 ms of host time per 8 ms chunk):
         # any `Net` call after a parameter change re-packs and replaces `net._packed`.  The streamer owns references to
         # the images its graphs point into, so a stale streamer is never unsafe, only out of date.
@@ -974,10 +1004,8 @@ class Streamer:
         if cur is not self._pk:
             raise RuntimeError("the Net's parameters changed after this Streamer was built (its HIP graphs hold pointers "
                                "into the old packed weights): create a new streamer with net.make_streamer(...)")
-        if net.range_check and int(self.range_flag[0]) != 0:     # host read of the pinned word: free
-            self.range_flag.zero_()
-            raise RuntimeError("LH_ERR_RANGE: an earlier chunk produced non-finite samples, emitted as zeros (inf / NaN in "
-                               "the input or in the carried state); reset() the streamer")
+
+    def _check_versions(self):
         # ... and a parameter updated IN PLACE (optimizer step, load_state_dict) without any other `Net` call in between
         # would replay silently on the old images: the tensors' version counters are re-checked three per chunk, round
         # robin (all ~130 within 0.4 s of audio).  Round 3 summed all of them every 64th chunk: ~0.13 ms of host time on
@@ -989,11 +1017,154 @@ class Streamer:
             if t._version != v:
                 raise RuntimeError("a parameter of the Net was modified in place after this Streamer was built: create a new "
                                    "streamer with net.make_streamer(...)")
-        self.chunk.copy_(chunk)
+
+
+class _Span(ctypes.Structure):
+    """`lh_span_t` (include/lookonce_hip.h): one tensor of per-slot streaming state."""
+    _fields_ = [("base", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
+
+
+class SessionStreamer:
+    """A batched `Streamer` whose rows are listener SLOTS that open, close and fail one at a time.
+
+    The chunk loop stays what `Streamer` runs — same buffers, same launches, all slots advance together, one chunk per
+    `step` — between two more graph nodes (include/lookonce_hip.h, "streaming sessions"): `lh_session_begin` zeroes the
+    state of a slot that was just opened or closed and hands only live slots' samples to the separator; `lh_session_end`
+    silences idle slots and closes a slot whose chunk was, or came out, non-finite.  A fault therefore costs ONE listener
+    their session: `step` never raises for it, the other rows keep their bits, and the slot can be opened again at once.
+      * `open(slot, embed)`: from the next `step` on the slot is a fresh stream (zero tails, (h, c) and K / V history — the
+        zero history is the same in every rotation of the ring, so the shared ring position needs no per-slot copy) with
+        its own speaker gain;  `close(slot)`: from the next `step` on its output rows are exact zeros;
+      * `set_embedding(slot, embed)` re-targets an open slot, its carried state is kept;
+      * `faults()`: slots the device closed since they were opened;  `active`: the open slots that have not faulted.
+    Nothing here waits for the device: commands travel as one asynchronous copy of a pinned array ahead of the replay
+    (only when something is pending), the fault words are pinned host memory the last kernel stores to.
+    Not built: idle slots still cost their share of every launch (rows are not compacted); slots advance in lock-step;
+    enrollment (`EmbedTFGridNet` -> `open`) is the caller's."""
+    RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
+
+    def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True):
+        if n_slots < 1:
+            raise ValueError("n_slots must be positive")
+        # buffers, packed weights, workspace and staleness checks are a Streamer's; its graphs are not captured
+        self._st = st = Streamer(net, n_slots, device, use_graph=False)
+        self.net, self.S, self.device = net, n_slots, st.device
+        S, dev = n_slots, st.device
+        self.chunk_in = torch.zeros_like(st.chunk)          # as the clients sent it; `st.chunk` is the gated copy
+        self.out = st.out
+        self._words = torch.zeros(3, S, dtype=torch.int32, device=dev)       # cmd from the host | cmd from the device | active
+        self._fault = net._host_words(S, dev)
+        self._fault_np = self._fault.numpy()                # the same memory, read without a tensor op per slot
+        span = lambda t: _Span(t.data_ptr(), t.numel() * t.element_size() // S)
+        state = [t for x in st.sets for t in [x["conv_buf"], x["deconv_buf"], x["istft_buf"]] + x["h"] + x["c"]]
+        state += [t for kv in st.rings for t in kv]
+        if len(state) > self.MAX_SPANS:
+            raise ValueError(f"{len(state)} state tensors, lh_session_begin takes {self.MAX_SPANS}")
+        self._spans = (_Span * len(state))(*[span(t) for t in state])
+        # what chunk k WRITES: the (h, c) of the other ping-pong set
+        self._spans_end = [(_Span * (2 * net.n_blocks))(*[span(t) for t in st.sets[k ^ 1]["h"] + st.sets[k ^ 1]["c"]])
+                           for k in (0, 1)]
+        self._gen = [0] * S                                 # generation of the slot's current opening, 0 = idle
+        self._next_gen = 1
+        self._pending = {}                                  # slot -> command word for the next step
+        self.graphs = None
+        if use_graph:
+            with torch.no_grad():
+                self.graphs = Streamer._capture(self._body, dev)
+            self.reset()
+
+    def _body(self, k: int):
+        st, net, S = self._st, self.net, self.S
+        P = lambda t: t.data_ptr()
+        with net._device_ctx(st.chunk):
+            lib, stream = net._lib(st.chunk), net._stream(self.device)
+            cmd, active = self._words.data_ptr(), self._words[2].data_ptr()
+            lib.call("lh_session_begin", ctypes.addressof(self._spans), len(self._spans), P(self.chunk_in), P(st.chunk), cmd,
+                     active, S, stream)
+            net._stream_chunk(st.chunk, st.gain, st.sets[k], st.sets[k ^ 1], st.rings, st.pos, st.out, st._pk, st._ws, None,
+                              keep_nonfinite=1)
+            lib.call("lh_ring_advance", P(st.pos), net.local_atten_len, stream)
+            lib.call("lh_session_end", ctypes.addressof(self._spans_end[k]), len(self._spans_end[k]), P(self.chunk_in),
+                     P(st.out), cmd, active, P(self._fault), S, stream)
+
+    def reset(self):
+        """Every slot idle, all state zero (what a new SessionStreamer starts from)."""
+        self._st.reset()
+        self._words.zero_()
+        self._fault.zero_()
+        self._gen = [0] * self.S
+        self._pending.clear()
+
+    def _slot(self, slot: int) -> int:
+        if not 0 <= slot < self.S:
+            raise IndexError(f"slot {slot} out of range for {self.S} slots")
+        return slot
+
+    def faults(self) -> list:
+        """Slots the device closed (non-finite input, or an fp32 overflow inside the separator) since their last `open`."""
+        f = self._fault_np
+        return [s for s, g in enumerate(self._gen) if g and int(f[s]) == g]
+
+    @property
+    def active(self) -> list:
+        """The host's view of the open slots: opened, not closed, no fault reported so far."""
+        f = self._fault_np
+        return [s for s, g in enumerate(self._gen) if g and int(f[s]) != g]
+
+    def _set_gain(self, slot: int, embed: torch.Tensor):
+        st = self._st
+        st.embed[slot].copy_(embed.reshape(-1), non_blocking=True)
+        with torch.no_grad():                               # this row only, eager, stream-ordered before the next replay
+            self.net._speaker_gain(st.embed[slot:slot + 1], st.gain_raw[slot:slot + 1], st.gain[slot:slot + 1])
+
+    def open(self, slot: int, embed: torch.Tensor):
+        """From the next `step` on `slot` is a fresh stream that listens for `embed` [256]."""
+        self._slot(slot)
+        if slot in self.active:
+            raise ValueError(f"slot {slot} is open: close() it first")
+        gen = self._next_gen
+        self._next_gen = gen % self.GEN_MASK + 1
+        # the fault word of the previous listener holds an older generation: cleared for the host as of now, and on the
+        # device by the chunk that opens the slot
+        self._gen[slot] = gen
+        self._pending[slot] = self.RESET | self.OPEN | (gen << self.GEN_SHIFT)
+        self._set_gain(slot, embed)
+
+    def close(self, slot: int):
+        """From the next `step` on `slot` is idle: its output rows are exact zeros.  Also acknowledges a fault."""
+        self._slot(slot)
+        if not self._gen[slot]:
+            raise ValueError(f"slot {slot} is not open")
+        self._gen[slot] = 0
+        self._pending[slot] = self.RESET | self.CLOSE
+
+    def set_embedding(self, slot: int, embed: torch.Tensor):
+        """Re-target an open slot ("look once" at another speaker): the carried state is kept."""
+        self._slot(slot)
+        if not self._gen[slot]:
+            raise ValueError(f"slot {slot} is not open")
+        self._set_gain(slot, embed)
+
+    def step(self, chunks: torch.Tensor) -> torch.Tensor:
+        """chunks [S, 2, 192] (rows of idle slots are ignored) -> [S, 2, 128] (rows of idle slots are zeros); a view the next
+        `step` overwrites.  Never raises for a slot's fault: see `faults()`."""
+        st = self._st
+        st._check_repacked()
+        st._check_versions()
+        if self._pending:
+            # a FRESH pinned array per batch of commands: the host allocator hands its memory out again only after the
+            # copy below has run, so a host that runs ahead of the device cannot overwrite commands in flight
+            src = self.net._host_words(self.S, self.device)
+            words = src.numpy()
+            for slot, w in self._pending.items():
+                words[slot] = w
+            self._pending.clear()
+            self._words[0].copy_(src, non_blocking=True)
+        self.chunk_in.copy_(chunks)
         with torch.no_grad():
             if self.graphs is not None:
-                self.graphs[self.parity].replay()
+                self.graphs[st.parity].replay()
             else:
-                self._body(self.parity)
-        self.parity ^= 1
+                self._body(st.parity)
+        st.parity ^= 1
         return self.out

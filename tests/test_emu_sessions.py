@@ -1,0 +1,356 @@
+"""CPU: `SessionStreamer` (net.py) and its two kernels (`lh_session_begin` / `lh_session_end`, lh_stream.hip) over the emulated
+library, eager.  Listener slots open, close, are re-used and fail one at a time while the batch goes on in lock-step.
+The reference of a session is the oracle's forward over the session's OWN samples from the zero state (streaming == offline,
+`O.predict(..., None, pad=False)`), within the emulator tolerance of tests/test_emu_kernels.py; isolation and equality
+claims are `torch.equal`.  Small on purpose (S <= 3, about ten chunks per case): the emulator runs a chunk row in ~0.5 s."""
+import ctypes
+
+import pytest
+import torch
+
+from lookoncetohear_amd import _cabi, synth
+from lookoncetohear_amd.net import SessionStreamer, _Span
+from tests.hipemu.hosts import EmuNet
+from oracle import tfgridnet_oracle as O
+
+TOL = 5e-5          # tests/test_emu_kernels.py
+HOP, NFFT = 128, 192
+
+
+class EmuSessionNet(EmuNet):
+    def _host_words(self, n, device):               # the pinned words of the GPU host: plain host memory here
+        return torch.zeros(n, dtype=torch.int32)
+
+
+@pytest.fixture(scope="module")
+def emu_net(oracle_cfg_sd):
+    from tests.hipemu.build_emu import build_emu
+    cfg, sd = oracle_cfg_sd
+    net = EmuSessionNet(**O.TSH_PARAMS).eval()
+    net.load_state_dict(sd, strict=True)
+    net.emu_lib = _cabi.Lib(build_emu())
+    return net
+
+
+@pytest.fixture(scope="module")
+def clips():
+    """Three 12-chunk binaural mixtures with their speaker embeddings."""
+    d = synth.batch([20, 21, 22], HOP * 12 + NFFT - HOP)
+    return d["mixture"], d["embedding_gt"][:, 0]
+
+
+def chunk_of(mix_row, j):
+    """Chunk j of one listener's stream [2, N] -> [2, 192]."""
+    return mix_row[:, j * HOP:j * HOP + NFFT]
+
+
+def fresh_stream(oracle_cfg_sd, mix_row, emb_row, n):
+    """The oracle's output for the first n chunks of a stream that starts from the zero state: [2, 128 n]."""
+    cfg, sd = oracle_cfg_sd
+    y, _ = O.predict(cfg, sd, mix_row[None, :, :HOP * n + NFFT - HOP], emb_row[None], None, pad=False)
+    return y[0]
+
+
+def run(ss, S, n, feed, events=None):
+    """n steps; feed(i) -> {slot: chunk [2, 192]} (rows not named are NaN: idle rows must be ignored), events {i: fn} run
+    before step i.  Returns [S, 2, 128 n]."""
+    outs = []
+    for i in range(n):
+        if events and i in events:
+            events[i]()
+        x = torch.full((S, 2, NFFT), float("nan"))
+        for slot, c in feed(i).items():
+            x[slot] = c
+        outs.append(ss.step(x).clone())
+    return torch.cat(outs, -1)
+
+
+def test_all_open_equals_streamer(emu_net, clips):
+    """Every slot opened before the first step: bit-identical to `Streamer` of the same batch on the same data."""
+    mix, emb = clips
+    S, n = 2, 6
+    st = emu_net.make_streamer(S, "cpu", use_graph=False)
+    st.set_embedding(emb[:S])
+    ss = emu_net.make_session_streamer(S, "cpu", use_graph=False)
+    assert isinstance(ss, SessionStreamer) and ss.active == [] and ss.faults() == []
+    for s in range(S):
+        ss.open(s, emb[s])
+    assert ss.active == [0, 1]
+    for i in range(n):
+        x = torch.stack([chunk_of(mix[s], i) for s in range(S)])
+        assert torch.equal(ss.step(x), st.step(x)), i
+    assert ss.active == [0, 1] and ss.faults() == []
+
+
+def test_staggered_open_and_close(emu_net, clips, oracle_cfg_sd):
+    """Slot 0 from chunk 0, slot 1 opened at chunk 3 (ring position 3, not 0) with its own embedding, slot 0 closed at
+    chunk 6."""
+    mix, emb = clips
+    S, n = 2, 9
+    ss = emu_net.make_session_streamer(S, "cpu", use_graph=False)
+    ss.open(0, emb[0])
+
+    def feed(i):
+        f = {}
+        if i < 6:
+            f[0] = chunk_of(mix[0], i)
+        if i >= 3:
+            f[1] = chunk_of(mix[1], i - 3)
+        return f
+    y = run(ss, S, n, feed, {3: lambda: ss.open(1, emb[1]), 6: lambda: ss.close(0)})
+    assert ss.active == [1]
+    # slot 1 from its opening on: the oracle's fresh stream of its own samples
+    ref1 = fresh_stream(oracle_cfg_sd, mix[1], emb[1], n - 3)
+    e1 = float((y[1, :, 3 * HOP:] - ref1).abs().max())
+    print("slot 1 opened at chunk 3: max|emu - oracle fresh stream| =", e1)
+    assert e1 < TOL
+    ref0 = fresh_stream(oracle_cfg_sd, mix[0], emb[0], 6)
+    assert float((y[0, :, :6 * HOP] - ref0).abs().max()) < TOL
+    # idle rows are exact zeros (their input rows were NaN)
+    assert torch.equal(y[1, :, :3 * HOP], torch.zeros(2, 3 * HOP)) and torch.equal(y[0, :, 6 * HOP:], torch.zeros(2, 3 * HOP))
+    assert ss.faults() == []
+    # slot 0 is bit-identical to a run in which slot 1 never opens
+    alone = emu_net.make_session_streamer(S, "cpu", use_graph=False)
+    alone.open(0, emb[0])
+    ya = run(alone, S, 6, lambda i: {0: chunk_of(mix[0], i)})
+    assert torch.equal(ya[0], y[0, :, :6 * HOP]) and torch.equal(ya[1], torch.zeros(2, 6 * HOP))
+
+
+def test_slot_reuse_keeps_nothing_of_the_previous_listener(emu_net, clips, oracle_cfg_sd):
+    """A slot closed after some chunks and opened again with another embedding — at once, and after an idle chunk — matches
+    the oracle's fresh stream: nothing survives in the tails, (h, c) or the rings."""
+    mix, emb = clips
+    ss = emu_net.make_session_streamer(1, "cpu", use_graph=False)
+    ss.open(0, emb[0])
+
+    def reopen(k):
+        ss.close(0)
+        ss.open(0, emb[k])
+    feed = lambda i: ({0: chunk_of(mix[0], i)} if i < 3 else {0: chunk_of(mix[1], i - 3)} if i < 6 else
+                      {} if i == 6 else {0: chunk_of(mix[2], i - 7)})
+    y = run(ss, 1, 10, feed, {3: lambda: reopen(1), 6: lambda: ss.close(0), 7: lambda: ss.open(0, emb[2])})
+    assert float((y[0, :, :3 * HOP] - fresh_stream(oracle_cfg_sd, mix[0], emb[0], 3)).abs().max()) < TOL
+    assert float((y[0, :, 3 * HOP:6 * HOP] - fresh_stream(oracle_cfg_sd, mix[1], emb[1], 3)).abs().max()) < TOL
+    assert torch.equal(y[0, :, 6 * HOP:7 * HOP], torch.zeros(2, HOP))
+    assert float((y[0, :, 7 * HOP:] - fresh_stream(oracle_cfg_sd, mix[2], emb[2], 3)).abs().max()) < TOL
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_fault_isolation(emu_net, clips, oracle_cfg_sd, bad):
+    """A non-finite sample in slot 1's chunk 2: no exception, the slot is reported and silent, slot 0 keeps its bits; the slot
+    opens again as a fresh stream."""
+    mix, emb = clips
+    S, n = 2, 8
+    clean = emu_net.make_session_streamer(S, "cpu", use_graph=False)
+    clean.open(0, emb[0]), clean.open(1, emb[1])
+    yc = run(clean, S, n, lambda i: {0: chunk_of(mix[0], i), 1: chunk_of(mix[1], i)})
+
+    ss = emu_net.make_session_streamer(S, "cpu", use_graph=False)
+    ss.open(0, emb[0]), ss.open(1, emb[1])
+    seen = {}
+
+    def feed(i):
+        f = {0: chunk_of(mix[0], i)}
+        if i < 5:
+            f[1] = chunk_of(mix[1], i).clone()
+            if i == 2:
+                f[1][1, 77] = bad
+        else:
+            f[1] = chunk_of(mix[2], i - 5)
+        return f
+
+    def look(i):
+        seen[i] = (ss.faults(), ss.active)
+    y = run(ss, S, n, feed, {2: lambda: look(2), 3: lambda: look(3), 5: lambda: (look(5), ss.open(1, emb[2]))})
+    assert seen[2] == ([], [0, 1]) and seen[3] == ([1], [0]) and seen[5] == ([1], [0])
+    assert torch.equal(y[0], yc[0])                                        # the neighbour never noticed
+    assert torch.equal(y[1, :, :2 * HOP], yc[1, :, :2 * HOP])
+    assert torch.equal(y[1, :, 2 * HOP:5 * HOP], torch.zeros(2, 3 * HOP))   # silent from the bad chunk on
+    e = float((y[1, :, 5 * HOP:] - fresh_stream(oracle_cfg_sd, mix[2], emb[2], 3)).abs().max())
+    print("re-opened after a fault: max|emu - oracle fresh stream| =", e)
+    assert e < TOL
+    assert ss.faults() == [] and ss.active == [0, 1]
+    assert torch.isfinite(y).all()
+
+
+def test_set_embedding_mid_stream_keeps_the_state(emu_net, clips, oracle_cfg_sd):
+    """`set_embedding(slot, ...)` at chunk 3 == the oracle's chunk loop that switches the embedding there, state carried."""
+    cfg, sd = oracle_cfg_sd
+    mix, emb = clips
+    n = 6
+    ss = emu_net.make_session_streamer(2, "cpu", use_graph=False)
+    ss.open(1, emb[0])
+    y = run(ss, 2, n, lambda i: {1: chunk_of(mix[0], i)}, {3: lambda: ss.set_embedding(1, emb[1])})
+    state, outs = None, []
+    for i in range(n):
+        yo, state = O.predict(cfg, sd, chunk_of(mix[0], i)[None], emb[0 if i < 3 else 1][None], state, pad=False)
+        outs.append(yo[0])
+    ref = torch.cat(outs, -1)
+    assert float((y[1] - ref).abs().max()) < TOL
+    # ... and the switch matters: the un-switched stream differs from chunk 3 on
+    assert float((ref[:, 3 * HOP:] - fresh_stream(oracle_cfg_sd, mix[0], emb[0], n)[:, 3 * HOP:]).abs().max()) > 100 * TOL
+
+
+def test_api_errors(emu_net, clips):
+    mix, emb = clips
+    ss = emu_net.make_session_streamer(2, "cpu", use_graph=False)
+    with pytest.raises(IndexError):
+        ss.open(2, emb[0])
+    with pytest.raises(IndexError):
+        ss.open(-1, emb[0])
+    with pytest.raises(IndexError):
+        ss.close(5)
+    with pytest.raises(IndexError):
+        ss.set_embedding(2, emb[0])
+    with pytest.raises(ValueError):
+        ss.close(0)                                  # not open
+    with pytest.raises(ValueError):
+        ss.set_embedding(0, emb[0])
+    ss.open(0, emb[0])
+    with pytest.raises(ValueError):
+        ss.open(0, emb[1])                           # already open
+    ss.close(0)
+    ss.open(0, emb[1])                               # close + open between two steps: the last word wins
+    assert ss.active == [0]
+    with pytest.raises(ValueError):
+        emu_net.make_session_streamer(0, "cpu", use_graph=False)
+    # the staleness checks of `Streamer.step`: a parameter modified in place, then weights re-packed by another Net call
+    y = ss.step(torch.zeros(2, 2, NFFT))
+    assert tuple(y.shape) == (2, 2, HOP)
+    p = next(emu_net.parameters())
+    keep = p.detach().clone()
+    try:
+        with torch.no_grad():
+            p.add_(0.0)
+        ss._st._vpos = 0
+        with pytest.raises(RuntimeError, match="modified in place"):
+            ss.step(torch.zeros(2, 2, NFFT))
+        emu_net(mix[:1, :, :320], emb[:1, None])
+        with pytest.raises(RuntimeError, match="parameters changed"):
+            ss.step(torch.zeros(2, 2, NFFT))
+    finally:
+        with torch.no_grad():
+            p.copy_(keep)
+
+
+# ---- the two entry points on hand-made buffers ---------------------------------------------------------------------------
+RESET, OPEN, CLOSE, SHIFT = 1, 2, 4, 8
+
+
+class Bench:
+    """S slots with two small state tensors (one also handed to the end kernel as "fresh (h, c)")."""
+
+    def __init__(self, lib, S):
+        self.lib, self.S = lib, S
+        self.a = torch.ones(S, 7, 4)                          # 112 bytes per slot
+        self.b = torch.ones(S * 3, 8, dtype=torch.float16)    # 48 bytes per slot
+        self.x = torch.randn(S, 2, NFFT)
+        self.gated = torch.full((S, 2, NFFT), 9.0)
+        self.out = torch.randn(S, 2, HOP)
+        self.words = torch.zeros(3, S, dtype=torch.int32)
+        self.fault = torch.zeros(S, dtype=torch.int32)
+        self.spans = (_Span * 2)(_Span(self.a.data_ptr(), 112), _Span(self.b.data_ptr(), 48))
+
+    def begin(self):
+        self.lib.call("lh_session_begin", ctypes.addressof(self.spans), 2, self.x.data_ptr(), self.gated.data_ptr(),
+                      self.words.data_ptr(), self.words[2].data_ptr(), self.S, None)
+
+    def end(self):
+        self.lib.call("lh_session_end", ctypes.addressof(self.spans), 1, self.x.data_ptr(), self.out.data_ptr(),
+                      self.words.data_ptr(), self.words[2].data_ptr(), self.fault.data_ptr(), self.S, None)
+
+
+def test_session_kernels_word_protocol(emu_net):
+    S = 3
+    k = Bench(emu_net.emu_lib, S)
+    out0 = k.out.clone()
+    # nothing pending, nobody open: state untouched, every slot gated to zero and silent
+    k.begin(), k.end()
+    assert torch.equal(k.a, torch.ones_like(k.a)) and torch.equal(k.b, torch.ones_like(k.b))
+    assert not k.gated.any() and not k.out.any() and not k.words.any() and not k.fault.any()
+    # open slot 1 (generation 5): only its slices are zeroed, only its samples pass; the words are consumed by the end kernel
+    k.out.copy_(out0)
+    k.fault[1] = 3                                            # the previous listener's fault
+    k.words[0, 1] = RESET | OPEN | (5 << SHIFT)
+    k.begin()
+    assert k.words[0, 1] != 0                                 # the begin kernel writes no word
+    assert not k.a[1].any() and not k.b[3:6].any() and k.a[0].eq(1).all() and k.a[2].eq(1).all() and k.b[:3].eq(1).all()
+    assert torch.equal(k.gated[1], k.x[1]) and not k.gated[0].any() and not k.gated[2].any()
+    k.a.fill_(1.0)
+    k.end()
+    assert k.words.tolist() == [[0, 0, 0], [0, 0, 0], [0, 5, 0]] and k.fault.tolist() == [0, 0, 0]
+    assert torch.equal(k.out[1], out0[1]) and not k.out[0].any() and not k.out[2].any()
+    # a replay with nothing pending touches no state
+    k.begin(), k.end()
+    assert k.a.eq(1).all() and k.words[2].tolist() == [0, 5, 0]
+    # overflow: a non-finite value in the fresh state (or the output) of a live slot closes it and posts RESET on the device side
+    k.out.copy_(out0)
+    k.a[1, 6, 3] = float("inf")
+    k.begin(), k.end()
+    assert k.words.tolist() == [[0, 0, 0], [0, RESET, 0], [0, 0, 0]] and k.fault.tolist() == [0, 5, 0] and not k.out[1].any()
+    k.words[0, 0] = RESET | OPEN | (6 << SHIFT)              # the host's copy lands in row 0: the device's RESET survives
+    k.begin()
+    assert not k.a[1].any() and not k.a[0].any() and k.a[2].eq(1).all()
+    k.end()
+    assert k.words.tolist() == [[0, 0, 0], [0, 0, 0], [6, 0, 0]] and k.fault.tolist() == [0, 5, 0]
+    # non-finite input of a live slot: gated to zero, state zeroed, closed, reported; of an idle slot: ignored
+    k.a.fill_(1.0)
+    k.out.copy_(out0)
+    k.x[0, 1, 191] = float("nan")
+    k.x[2, 0, 0] = float("-inf")
+    k.begin(), k.end()
+    assert not k.gated.any() and not k.a[0].any() and k.a[1].eq(1).all() and k.a[2].eq(1).all()
+    assert k.words.tolist() == [[0, 0, 0], [0, 0, 0], [0, 0, 0]] and k.fault.tolist() == [6, 5, 0] and not k.out.any()
+    # output overflow alone
+    k.x.normal_()
+    k.words[0, 2] = RESET | OPEN | (7 << SHIFT)
+    k.out.copy_(out0)
+    k.out[2, 1, 127] = float("nan")
+    k.begin(), k.end()
+    assert k.words.tolist() == [[0, 0, 0], [0, 0, RESET], [0, 0, 0]] and k.fault.tolist() == [6, 5, 7] and not k.out.any()
+    # close
+    k.words[0, 2] = RESET | OPEN | (8 << SHIFT)
+    k.out.copy_(out0)
+    k.begin(), k.end()
+    assert k.words[2].tolist() == [0, 0, 8] and k.fault.tolist() == [6, 5, 0] and torch.equal(k.out[2], out0[2])
+    k.words[0, 2] = RESET | CLOSE
+    k.begin(), k.end()
+    assert not k.words.any() and not k.out.any()
+
+
+def test_session_entry_points_validate_arguments(emu_net):
+    lib = emu_net.emu_lib
+    k = Bench(lib, 2)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    sp = ctypes.c_void_p(ctypes.addressof(k.spans))
+    cmd, act = P(k.words), P(k.words[2])
+    begin, end = lib.raw("lh_session_begin"), lib.raw("lh_session_end")
+    ARG = 1
+    assert begin(sp, 2, P(k.x), P(k.gated), cmd, act, 2, None) == 0
+    assert end(sp, 2, P(k.x), P(k.out), cmd, act, P(k.fault), 2, None) == 0
+    assert begin(None, 2, P(k.x), P(k.gated), cmd, act, 2, None) == ARG
+    assert begin(sp, 2, None, P(k.gated), cmd, act, 2, None) == ARG
+    assert begin(sp, 2, P(k.x), None, cmd, act, 2, None) == ARG
+    assert begin(sp, 2, P(k.x), P(k.x), cmd, act, 2, None) == ARG          # gated copy must not alias the input
+    assert begin(sp, 2, P(k.x), P(k.gated), None, act, 2, None) == ARG
+    assert begin(sp, 2, P(k.x), P(k.gated), cmd, None, 2, None) == ARG
+    assert begin(sp, 2, P(k.x), P(k.gated), cmd, act, 0, None) == ARG
+    assert begin(sp, 0, P(k.x), P(k.gated), cmd, act, 2, None) == ARG
+    assert begin(sp, 33, P(k.x), P(k.gated), cmd, act, 2, None) == ARG
+    assert end(None, 2, P(k.x), P(k.out), cmd, act, P(k.fault), 2, None) == ARG
+    assert end(sp, 2, None, P(k.out), cmd, act, P(k.fault), 2, None) == ARG
+    assert end(sp, 2, P(k.x), None, cmd, act, P(k.fault), 2, None) == ARG
+    assert end(sp, 2, P(k.x), P(k.out), None, act, P(k.fault), 2, None) == ARG
+    assert end(sp, 2, P(k.x), P(k.out), cmd, None, P(k.fault), 2, None) == ARG
+    assert end(sp, 2, P(k.x), P(k.out), cmd, act, None, 2, None) == ARG
+    assert end(sp, 2, P(k.x), P(k.out), cmd, act, P(k.fault), -1, None) == ARG
+    nine = (_Span * 9)(*[_Span(k.a.data_ptr(), 112)] * 9)      # lh_session_end: at most LH_SESSION_MAX_END_SPANS = 8
+    q9 = ctypes.c_void_p(ctypes.addressof(nine))
+    assert begin(q9, 9, P(k.x), P(k.gated), cmd, act, 2, None) == 0
+    assert end(q9, 8, P(k.x), P(k.out), cmd, act, P(k.fault), 2, None) == 0
+    assert end(q9, 9, P(k.x), P(k.out), cmd, act, P(k.fault), 2, None) == ARG
+    for bad in (_Span(k.a.data_ptr(), 100), _Span(k.a.data_ptr(), 0), _Span(None, 112), _Span(k.a.data_ptr() + 4, 112)):
+        spans = (_Span * 2)(_Span(k.b.data_ptr(), 48), bad)          # size not a multiple of the store width, empty, null, unaligned
+        q = ctypes.c_void_p(ctypes.addressof(spans))
+        assert begin(q, 2, P(k.x), P(k.gated), cmd, act, 2, None) == ARG
+        assert end(q, 2, P(k.x), P(k.out), cmd, act, P(k.fault), 2, None) == ARG
