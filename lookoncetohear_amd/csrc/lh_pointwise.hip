@@ -127,6 +127,10 @@ struct HeadLN {
             b[k] = *reinterpret_cast<const float4*>(&gb[4 * o]);
         }
     }
+    __device__ __forceinline__ void set_affine(const HeadLN& o) {               // affine held by the caller across frames
+#pragma unroll
+        for (int k = 0; k < NS; ++k) { w[k] = o.w[k]; b[k] = o.b[k]; }
+    }
     __device__ __forceinline__ float center(float mean, int lane) {             // x -= mean; lane's partial sum of squares
         float v = 0.f;
 #pragma unroll
@@ -178,6 +182,65 @@ __device__ unsigned long long lh_qkv_trace_buf[16];
 #define QKV_STAMP(k) do { } while (0)
 #endif
 
+// The product phase of k_qkv_proj_ln for one wave: its one (wave 3: V columns 48..63) or two (waves 0..2: Q | K columns
+// 16w.. and V columns 64+16w..) column tiles against the 7 row tiles of the frame.  Until this form the seven tiles ran
+// one after the other from a rolled loop — LDS reads, wait, one chain of 6 dependent MFMAs, wait, epilogue, then the same
+// for the second column tile — so a wave exposed the LDS latency, two accumulator read-outs and the chain length seven
+// times per frame with nothing of its own to issue meanwhile.  Now stage m of 8 issues the LDS reads of row tile m + 1 and
+// the inverse row scales of tile m, then zips (lh_recur.hip: one MFMA step, a slice of vector work, a scheduling fence) the
+// two chains of tile m — independent, so one fills the other's dependency gap — with the epilogue of tile m - 1.
+// Each chain keeps its order (lo.hi, hi.lo, hi.hi per k-step, k-steps ascending: mma_tile1) and each output element its
+// arithmetic, so the results are bit-identical.  The stages are unrolled with the fences in place (the plain unroll of
+// the old loop let the scheduler hoist all 28 reads and spilled): every LDS address is lane base + immediate.
+// TWO is wave-uniform (waves 0..2) and also fixes the row stride of the first tile in `yf`: E for Q / K, VD for V.
+// Row tile 6 holds one valid row (96: g4 == 0, r == 0); its other 15 rows get neither arithmetic nor a store.
+template <bool TWO, bool FAST>
+__device__ __forceinline__ void qkv_products(const _Float16* ahi, const _Float16* alo, const float* rinv, float* yf, int g4, int l15,
+                                             const f16x8 (&wh0)[2], const f16x8 (&wl0)[2], const f16x8 (&wh1)[2],
+                                             const f16x8 (&wl1)[2], float bz0, float bz1, float a0, float sv, int base0, int base1) {
+    constexpr int NT = FR_RP / 16, STR0 = TWO ? E : VD;
+    static_assert(2 * NH * E == 3 * 16 && NQKV / 16 == 7, "waves 0..2: a Q | K tile and a V tile; wave 3: one V tile");
+    ATile a[2];
+    float4 iv[2];
+    f32x4 r0[2], r1[2];
+    float* y0 = yf + base0 + g4 * 4 * STR0;
+    float* y1 = yf + base1 + g4 * 4 * VD;
+    a_tile_read<FR_RP>(a[0], ahi, alo, 0, g4, l15);
+    xp_for<NT + 1>([&](auto m_) {
+        constexpr int m = decltype(m_)::value, cur = m & 1, prv = cur ^ 1;
+        if (m + 1 < NT) a_tile_read<FR_RP>(a[prv], ahi, alo, m + 1, g4, l15);
+        if (m < NT) iv[cur] = *reinterpret_cast<const float4*>(&rinv[m * 16 + g4 * 4]);      // 1 / scale of this lane's 4 rows
+        __builtin_amdgcn_sched_barrier(0);
+        // epilogue of row r of tile m - 1: bias + PReLU -> yf, already in each head's LayerNorm order
+        auto epilogue = [&](auto r_) {
+            constexpr int r = decltype(r_)::value, row = (m - 1) * 16 + r;      // + 4 g4: in y0 / y1
+            const float ivr = r == 0 ? iv[prv].x : r == 1 ? iv[prv].y : r == 2 ? iv[prv].z : iv[prv].w;
+            const float z0 = fmaf(r0[prv][r], ivr, bz0);
+            y0[row * STR0] = FAST ? prelu_mm<true>(z0, a0) : prelu_f(z0, a0);
+            if (TWO) {
+                const float z1 = fmaf(r1[prv][r], ivr, bz1);
+                y1[row * VD] = FAST ? prelu_mm<true>(z1, sv) : prelu_f(z1, sv);
+            }
+        };
+        if (m < NT) {
+            xp_for<6>([&](auto s_) {
+                constexpr int s = decltype(s_)::value, ks = s / 3, j = s % 3;
+                const f16x8 av = j == 0 ? a[cur].l[ks] : a[cur].h[ks];
+                const f32x4 c0 = s == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : r0[cur];
+                r0[cur] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, j == 1 ? wl0[ks] : wh0[ks], c0, 0, 0, 0);
+                if (TWO) {
+                    const f32x4 c1 = s == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : r1[cur];
+                    r1[cur] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, j == 1 ? wl1[ks] : wh1[ks], c1, 0, 0, 0);
+                }
+                if (m > 0 && s >= 1 && s <= 4) epilogue(std::integral_constant<int, s - 1>{});
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        } else if (g4 == 0) {
+            epilogue(std::integral_constant<int, 0>{});
+        }
+    });
+}
+
 __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict__ y, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slopes,
                                                      const float* __restrict__ lnq_w, const float* __restrict__ lnq_b,
@@ -208,10 +271,11 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
     const float a0 = c0 < NH * E ? sq : (c0 < 2 * NH * E ? sk : sv);      // PReLU slope of column c0; c1 is always V
     const bool le1 = sq <= 1.0f && sk <= 1.0f && sv <= 1.0f;            // kernel-uniform: PReLU = max(x, a x)
     // where this lane's columns land in yf: element (f, c) -> base + f * stride
-    int base0, str0;
-    if (c0 < NH * E) { base0 = (c0 / E) * YQS + c0 % E; str0 = E; }
-    else if (c0 < 2 * NH * E) { base0 = Y_K0 + ((c0 - NH * E) / E) * YQS + (c0 - NH * E) % E; str0 = E; }
-    else { base0 = Y_V0 + ((c0 - 2 * NH * E) / VD) * DV + (c0 - 2 * NH * E) % VD; str0 = VD; }
+    // (row stride E for Q / K = waves 0..2, VD for V = wave 3: a template argument of qkv_products)
+    int base0;
+    if (c0 < NH * E) base0 = (c0 / E) * YQS + c0 % E;
+    else if (c0 < 2 * NH * E) base0 = Y_K0 + ((c0 - NH * E) / E) * YQS + (c0 - NH * E) % E;
+    else base0 = Y_V0 + ((c0 - 2 * NH * E) / VD) * DV + (c0 - 2 * NH * E) % VD;
     const int cv = (two ? c1 : c0) - 2 * NH * E;                  // second tile: always V columns (unused when !two)
     const int base1 = Y_V0 + (cv / VD) * DV + cv % VD;
 
@@ -219,6 +283,12 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
     if (tid < FR_RP - NF) rinv[NF + tid] = 0.f;                // pad rows: finite
     for (int i = tid; i < 2 * NH * (YQS - DQK); i += 256)      // pad entries 582.. of the Q / K heads stay zero
         yf[(i / (YQS - DQK)) * YQS + DQK + i % (YQS - DQK)] = 0.f;
+    // The Q and K LayerNorm affine of this lane's quads stays in registers for the whole persistent loop (48 VGPRs: the
+    // rows are shared by all heads and a lane's quads never change).  V's 56 do not fit next to them (249 of 256 VGPRs
+    // now) and are still fetched per frame, under the Q / K arithmetic.
+    HeadLN<DQK, 2 * QKB> aq, ak;
+    aq.load_affine(lnq_w, lnq_b, lane);
+    ak.load_affine(lnk_w, lnk_b, lane);
     float4 stg[FR_NLD];
     if ((int)blockIdx.x < nframes) frame_load(y + gidx(blockIdx.x) * NF * C, tid, stg);
     const long tkp = T + HIST + KV_PAD;
@@ -234,38 +304,15 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
         QKV_STAMP(1);
         if (fr + (int)gridDim.x < nframes) frame_load(y + gidx(fr + gridDim.x) * NF * C, tid, stg);   // prefetch
 
-        // row tiles 0..5 hold rows 0..95 (all valid); only tile 6 (rows 96..111, one valid) needs the bounds check.
-        // Round 5 (the kernel is VALU-bound): one accumulator chain per tile (no am + ac adds) and PReLU
-        // as max / min (two instructions instead of three; `le1`: all three slopes <= 1, the usual case, else the
-        // compare + select form).  (Unrolling the seven tiles for immediate LDS offsets was tried: 256 VGPRs + 9 spilled.)
-        auto row_tile = [&](int m, auto checked, auto fast) {
-            const f32x4 r0 = mma_tile1<FR_RP, 2>(ahi, alo, m, g4, l15, wh0, wl0, 0.f);
-            const float4 iv4 = *reinterpret_cast<const float4*>(&rinv[m * 16 + g4 * 4]);     // 1 / scale of this lane's 4 rows
-            const float iv[4] = {iv4.x, iv4.y, iv4.z, iv4.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m * 16 + g4 * 4 + r;
-                const float z = fmaf(r0[r], iv[r], bz0);
-                if (!checked.value || row < NF) yf[base0 + row * str0] = fast.value ? prelu_mm<true>(z, a0) : prelu_f(z, a0);
-            }
-            if (two) {
-                const f32x4 r1 = mma_tile1<FR_RP, 2>(ahi, alo, m, g4, l15, wh1, wl1, 0.f);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = m * 16 + g4 * 4 + r;
-                    const float z = fmaf(r1[r], iv[r], bz1);
-                    if (!checked.value || row < NF) yf[base1 + row * VD] = fast.value ? prelu_mm<true>(z, sv) : prelu_f(z, sv);
-                }
-            }
-        };
-        if (le1) {
-#pragma unroll 1
-            for (int m = 0; m < NF / 16; ++m) row_tile(m, std::false_type{}, std::true_type{});
-            row_tile(NF / 16, std::true_type{}, std::true_type{});
+        // The 7 row tiles as a software pipeline (stage m: LDS reads of tile m + 1 | MFMAs of tile m | epilogue of tile m - 1),
+        // unrolled so that every LDS address is an immediate: qkv_products above.  PReLU as max / min when all three slopes
+        // are <= 1 (`le1`, the usual case), else the compare + select form.
+        if (two) {
+            if (le1) qkv_products<true, true>(ahi, alo, rinv, yf, g4, l15, wh0, wl0, wh1, wl1, bz0, bz1, a0, sv, base0, base1);
+            else qkv_products<true, false>(ahi, alo, rinv, yf, g4, l15, wh0, wl0, wh1, wl1, bz0, bz1, a0, sv, base0, base1);
         } else {
-#pragma unroll 1
-            for (int m = 0; m < NF / 16; ++m) row_tile(m, std::false_type{}, std::false_type{});
-            row_tile(NF / 16, std::true_type{}, std::false_type{});
+            if (le1) qkv_products<false, true>(ahi, alo, rinv, yf, g4, l15, wh0, wl0, wh1, wl1, bz0, bz1, a0, sv, base0, base1);
+            else qkv_products<false, false>(ahi, alo, rinv, yf, g4, l15, wh0, wl0, wh1, wl1, bz0, bz1, a0, sv, base0, base1);
         }
         QKV_STAMP(2);
         __syncthreads();
@@ -282,12 +329,12 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
         _Float16* krow = kx + (bh * tkp + krow0 + t) * LDQKH;
         _Float16* vrow = vx + (bh * tkp + krow0 + t) * LDVH;
         // `fr >> 30` is always 0 but ties the lane index to the loop variable: without it LICM hoists every slot address
-        // of the three rows out of the persistent frame loop and the kernel spills
+        // of the three rows (and V's affine) out of the persistent frame loop and the kernel spills
         const int ln = lane + (fr >> 30);
         {   // Q and K together: two independent statistics chains
             HeadLN<DQK, 2 * QKB> lq, lk;
-            lq.load_affine(lnq_w, lnq_b, ln);
-            lk.load_affine(lnk_w, lnk_b, ln);
+            lq.set_affine(aq);
+            lk.set_affine(ak);
             const float sq1 = lq.read(yq, zero8, ln), sk1 = lk.read(yk, zero8, ln);
             const float mq = wave_sum(sq1) * (1.0f / DQK), mk = wave_sum(sk1) * (1.0f / DQK);
             const float vq = lq.center(mq, ln), vk = lk.center(mk, ln);

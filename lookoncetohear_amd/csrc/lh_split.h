@@ -74,6 +74,20 @@ __device__ __forceinline__ f32x4 mma_tile1(const _Float16* ahi, const _Float16* 
     return am;
 }
 
+// The A fragments of one row tile for K = 64 (both k-steps, hi and lo) as a value, so that a kernel can read tile m + 1
+// while the MFMAs of tile m run.  With m a constant the swizzle leaves it out of the lane part: (16 m + l15) ^ b =
+// 16 m + (l15 ^ b) for b < 8, so the tile index becomes an immediate offset.
+struct ATile { f16x8 h[2], l[2]; };
+template <int RP>
+__device__ __forceinline__ void a_tile_read(ATile& a, const _Float16* ahi, const _Float16* alo, int m, int g4, int l15) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        const int idx = a_slot<RP>(ks * 4 + g4, l15) + m * 16 * 8;
+        a.h[ks] = *reinterpret_cast<const f16x8*>(&ahi[idx]);
+        a.l[ks] = *reinterpret_cast<const f16x8*>(&alo[idx]);
+    }
+}
+
 // weight image: [n-tile][kstep][lane][hi 8 | lo 8] fp16 (weights.py: pack_linear_f16x3)
 template <int KS>
 __device__ __forceinline__ void load_w(const _Float16* __restrict__ w_pk, int nt, int lane, f16x8 (&wh)[KS],
