@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (16); bumped on any signature change. */
+/* ABI version of this header (17); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -466,7 +466,7 @@ int lh_metric_sums(const float* outputs, const float* target, const float* mixtu
 int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B, int n_samples,
                      int sr, int frame, double rms_threshold, lh_stream_t stream);
 
-/* ---- streaming sessions (ABI 16) --------------------------------------------------------------------------------------------
+/* ---- streaming sessions (ABI 16, 17) ----------------------------------------------------------------------------------------
  * A batched streaming host serves S listener SLOTS in lock-step (one 8 ms chunk of every slot per step; slot = batch row of
  * every streaming entry point above).  These two launches bracket the chunk's launch sequence — first and last node of a
  * captured per-chunk graph — and let slots open, close and fail one at a time, on the device and without a host wait (the
@@ -507,6 +507,33 @@ int lh_session_begin(const lh_span_t* spans, int n_spans, const float* chunk_in,
                      const unsigned* active, int S, lh_stream_t stream);
 int lh_session_end(const lh_span_t* spans, int n_spans, const float* chunk_in, float* out, unsigned* cmd, unsigned* active,
                    unsigned* fault, int S, lh_stream_t stream);
+
+/* Enrollment capture (ABI 17): "look once" from the listener's own stream.  One more node of the per-chunk graph, right after
+ * lh_session_begin, in a host built for enrollment: an ARMED slot's next n_chunks input rows are recorded on the device, and a
+ * word in pinned host memory tells the host when the clip is complete — the host then runs the enrollment embedder
+ * (lh_emb_*) on it beside the chunk loop and opens the slot (LH_SESSION_OPEN) with the result, never waiting for the device.
+ *   chunk_in   [S][2][192] as above (never written)
+ *   enroll     [S][2][128 * n_chunks] fp32, 16-byte aligned: slot s, channel ch, chunk k of the capture -> samples
+ *              [128 k, 128 k + 128) = samples [0, 128) of chunk_in[s][ch].  The 64 look-ahead samples of a row are the first
+ *              64 new samples of the next row and are not recorded twice: a complete clip is the 128 * n_chunks contiguous
+ *              stream samples from the arming chunk on.
+ *   ecmd       [S] posted by the host like cmd (one asynchronous copy ahead of the step, only when something is pending):
+ *              LH_ENROLL_ARM | generation << LH_ENROLL_GEN_SHIFT (generation in 1 .. 2^23 - 1), or LH_ENROLL_CANCEL.
+ *              Consumed here: a posted word is written back as 0.
+ *   estate     [2][S] device-owned, zero at start: row 0 the generation being captured (0 = none), row 1 the chunks recorded
+ *   edone      [S] DEVICE-ACCESSIBLE words the host reads in place (pinned host memory, system-scope vector stores, like
+ *              fault): `generation` once the n_chunks-th chunk is recorded, `generation | LH_ENROLL_FAULT` when the capture
+ *              was aborted.  The clip itself is for stream-ordered readers: enqueue them after having seen the word.
+ * Per slot and chunk (one wave per slot, the only writer of the slot's words and clip): CANCEL clears the state and writes
+ * nothing to edone; ARM sets the generation and the count to 0 — also in mid-capture, which starts again; an armed slot
+ * whose 256 samples to record hold an inf / NaN is disarmed with the FAULT word (a non-finite look-ahead sample alone is
+ * judged when it becomes a recorded sample, in the next chunk); otherwise the samples are stored at the count, the count
+ * advances and at n_chunks the slot is disarmed with the done word.  A disarmed slot's clip is not written until the next ARM.
+ * The count lives on the device: the two alternating graphs have fixed arguments and a capture crosses both.
+ * LH_ERR_ARG: null pointer, S <= 0, n_chunks < 1, chunk_in or enroll not 16-byte aligned.  Neither allocates nor synchronises. */
+enum { LH_ENROLL_ARM = 1, LH_ENROLL_CANCEL = 2, LH_ENROLL_GEN_SHIFT = 8, LH_ENROLL_FAULT = 0x80000000u };
+int lh_session_capture(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone, int n_chunks,
+                       int S, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -36,6 +36,8 @@ SIGNATURES = {
     # streaming sessions (ABI 16): first / last node of a SessionStreamer's per-chunk graph
     "lh_session_begin": [_P, _I, _P, _P, _P, _P, _I, _P],
     "lh_session_end": [_P, _I, _P, _P, _P, _P, _P, _I, _P],
+    # enrollment capture (ABI 17): the node after lh_session_begin in a SessionStreamer built with enroll_chunks
+    "lh_session_capture": [_P] * 5 + [_I, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)

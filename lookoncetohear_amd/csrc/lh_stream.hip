@@ -348,6 +348,50 @@ __global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, const float
     }
 }
 
+// Enrollment capture (ABI 17): one more node of the per-chunk graph, right after k_session_begin, in a streamer built for
+// enrollment.  An armed slot records the 128 NEW samples of both channels of its input row at the device-side chunk count —
+// the 64 look-ahead samples are the head of the next chunk's row and are recorded (and judged) then.  One wave per slot: 64
+// lanes x one float4 are the 256 samples, and that wave is the only writer of the slot's words and of its clip.  Pure latency
+// like the two kernels above, so the three words and the lane's float4 are requested together before any is looked at.
+// The clip is read by stream-ordered work only (the host enqueues the embedder behind an event it records after it has seen
+// the done word), so the done word needs no release: it tells the host WHICH chunk finished the clip, not that the bytes
+// are visible to the host.
+constexpr int SC_NT = 64;
+static_assert(NMIC * HOP / 4 == SC_NT && HOP / 4 == 32, "one float4 per lane: lane = 32 channel + float4 of the channel");
+__global__ void __launch_bounds__(SC_NT) k_session_capture(const float* __restrict__ chunk_in, float* __restrict__ enroll,
+                                                           unsigned* ecmd, unsigned* estate, unsigned* edone, int n_chunks,
+                                                           int S) {
+    const int s = blockIdx.x, lane = threadIdx.x, ch = lane >> 5, q = lane & 31;
+    const unsigned cmd = ecmd[s];
+    unsigned gen = estate[s], k = estate[S + s];
+    const float4 v = reinterpret_cast<const float4*>(chunk_in + ((long)s * NMIC + ch) * NFFT)[q];
+    if (cmd & LH_ENROLL_CANCEL) gen = 0u;
+    if (cmd & LH_ENROLL_ARM) {                     // also mid-capture: starts again under the new generation
+        gen = (cmd >> LH_ENROLL_GEN_SHIFT) & 0x7fffffu;
+        if (gen == 0u) gen = 1u;
+        k = 0u;
+    }
+    if (cmd == 0u && gen == 0u) return;            // wave-uniform: an idle slot with nothing posted costs the loads above
+    unsigned done = 0u;
+    if (gen != 0u) {
+        if (wave_any(nonfinite4(v))) {
+            done = gen | LH_ENROLL_FAULT;
+        } else {
+            k = min(k, (unsigned)n_chunks - 1u);   // the count is device-owned and < n_chunks; never index past the clip
+            reinterpret_cast<float4*>(enroll + ((long)s * NMIC + ch) * HOP * n_chunks + (long)HOP * k)[q] = v;
+            if (++k == (unsigned)n_chunks) done = gen;
+        }
+    }
+    if (done != 0u || gen == 0u) gen = 0u, k = 0u;
+    if (lane == 0) {
+        if (cmd != 0u) ecmd[s] = 0u;
+        estate[s] = gen;
+        estate[S + s] = k;
+        // pinned host memory the host reads in place, like fault[S]
+        if (done != 0u) __hip_atomic_store(&edone[s], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -412,5 +456,15 @@ extern "C" int lh_session_end(const lh_span_t* spans, int n_spans, const float* 
     if (!chunk_in || !out || !cmd || !active || !fault || S <= 0 || n_spans > SE_SP || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
     hipLaunchKernelGGL(k_session_end, dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, chunk_in, out, cmd, active, fault, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_capture(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone,
+                                  int n_chunks, int S, lh_stream_t stream) {
+    using namespace lh;
+    if (!chunk_in || !enroll || !ecmd || !estate || !edone || S <= 0 || n_chunks < 1) return LH_ERR_ARG;
+    if (((unsigned long long)(size_t)enroll & 15) || ((unsigned long long)(size_t)chunk_in & 15)) return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_capture, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate, edone,
+                       n_chunks, S);
     return check_launch();
 }

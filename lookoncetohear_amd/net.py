@@ -153,8 +153,56 @@ class _Lanes:
             self.main.wait_stream(s_)
 
 
+class _EnrollSide:
+    """The ONE side stream a `SessionStreamer` runs the enrollment embedder on, with the two events of a call and the "is it
+    done" query (one stream only: the process has four hardware queues and `time_chunks` uses lanes of its own).  The only
+    stream / event calls of enrollment live here; the emulator tests substitute a synchronous stand-in, as for `_Lanes`."""
+
+    def __init__(self, dev, low_priority: bool = False):
+        self.dev = dev
+        self._hip, self._raw = None, None
+        if low_priority:
+            # torch hands out default- and high-priority streams only: the lowest priority comes from the HIP runtime itself
+            # (dlsym on the library's handle searches its dependencies, i.e. the runtime that owns torch's streams too)
+            hip = self._hip = _cabi.load()._dll
+            least, greatest, raw = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                if (hip.hipDeviceGetStreamPriorityRange(ctypes.byref(least), ctypes.byref(greatest)) != 0 or
+                        hip.hipStreamCreateWithPriority(ctypes.byref(raw), 1, least.value) != 0):     # 1: non-blocking
+                    raise RuntimeError("could not create a low-priority HIP stream")
+            self._raw = raw
+            self.stream = torch.cuda.ExternalStream(raw.value, device=dev)
+        else:
+            self.stream = torch.cuda.Stream(device=dev)
+
+    def __del__(self):
+        if self._raw is not None:
+            self._hip.hipStreamDestroy(self._raw)      # asynchronous: the runtime frees it once its work has drained
+
+    def run(self, fn):
+        """fn() on the side stream, after everything enqueued so far on the loop's (current) stream -> (result, done event)."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self.stream.wait_event(ev)
+        with torch.cuda.stream(self.stream):
+            out = fn()
+        done = torch.cuda.Event()
+        done.record(self.stream)
+        return out, done
+
+    def finished(self, done) -> bool:
+        return done.query()
+
+    def hand_over(self, done, out: torch.Tensor):
+        """The loop's stream may read `out` from here on (`done` has completed: the wait costs the device nothing)."""
+        main = torch.cuda.current_stream(self.dev)
+        main.wait_event(done)
+        out.record_stream(main)
+
+
 class Net(_cabi.HipHost, nn.Module):
     _host_name = "Net"
+    enroll_low_priority = False      # priority of a SessionStreamer's embedder stream: see `_EnrollSide`, DESIGN.md
 
     def __init__(self, stft_chunk_size=160, stft_pad_size=120, embed_dim=256,
                  num_ch=2, D=64, B=6, I=1, J=1, L=0, H=128,
@@ -299,9 +347,14 @@ class Net(_cabi.HipHost, nn.Module):
         """Chunked real-time front end (BASELINE configs[1]): see `Streamer`."""
         return Streamer(self, batch_size, device, use_graph)
 
-    def make_session_streamer(self, n_slots: int, device, use_graph: bool = True):
-        """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`."""
-        return SessionStreamer(self, n_slots, device, use_graph)
+    def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0):
+        """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
+        `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
+        enrollment embedder runs beside the chunk loop and the slot opens itself on the result."""
+        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks)
+
+    def _enroll_side(self, dev) -> _EnrollSide:
+        return _EnrollSide(dev, self.enroll_low_priority)
 
     # ------------------------------------------------------------------------------------------------
     # host-side plumbing
@@ -1039,13 +1092,30 @@ class SessionStreamer:
       * `faults()`: slots the device closed since they were opened;  `active`: the open slots that have not faulted.
     Nothing here waits for the device: commands travel as one asynchronous copy of a pinned array ahead of the replay
     (only when something is pending), the fault words are pinned host memory the last kernel stores to.
-    Not built: idle slots still cost their share of every launch (rows are not compacted); slots advance in lock-step;
-    enrollment (`EmbedTFGridNet` -> `open`) is the caller's."""
+    Enrollment (`enroll_chunks` = n >= 2; 0, the default, builds exactly the object above): "look once" from the listener's
+    own stream.  `enroll(slot, embedder)` arms an idle slot: one more graph node (`lh_session_capture`, after
+    `lh_session_begin`) records the slot's next n chunks — the 128 n contiguous samples from the next `step` on — into a
+    device buffer and posts a word in pinned host memory when the clip is complete.  `poll()` (the first thing `step` does;
+    public, cheap, idempotent) reads those words: the clips completed since the last poll go through ONE `embedder` call, a
+    batch in ascending slot order, on the streamer's one side stream behind an event of the loop's stream; a call whose
+    second event reports complete hands its rows to the `open` path, and the slot is in `active` and a fresh stream from that
+    `step` on.  `enrolling`: the slots capturing or embedding;  `embedding_of(slot)`: the [256] device tensor enrollment
+    opened the slot with (keep it to `open` the listener again later).  Meanwhile the slot is idle to the separator: its
+    output rows are exact zeros — a host that wants pass-through audio during the look does that itself.  An inf / NaN among
+    the recorded samples aborts the capture: the slot is listed by `faults()` and is idle again, to be enrolled or opened at
+    once.  `close(slot)` cancels a capture or a running embedding (a result that arrives later is dropped by its
+    generation), `reset()` cancels all of them.  Call the embedder once on a clip of this length before the loop starts:
+    its first call packs weights.
+    Not built: idle slots still cost their share of every launch (rows are not compacted); slots advance in lock-step."""
     RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
+    ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
 
-    def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True):
+    def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
+        if enroll_chunks < 0 or enroll_chunks == 1:
+            raise ValueError("enroll_chunks must be 0 (no enrollment) or >= 2: the embedder needs 4 STFT frames at stride 64, "
+                             "192 samples, and a chunk records 128")
         # buffers, packed weights, workspace and staleness checks are a Streamer's; its graphs are not captured
         self._st = st = Streamer(net, n_slots, device, use_graph=False)
         self.net, self.S, self.device = net, n_slots, st.device
@@ -1067,6 +1137,19 @@ class SessionStreamer:
         self._gen = [0] * S                                 # generation of the slot's current opening, 0 = idle
         self._next_gen = 1
         self._pending = {}                                  # slot -> command word for the next step
+        self.enroll_chunks = n = enroll_chunks
+        self._capturing = {}                                # slot -> (generation, embedder) of a capture in progress
+        self._embedding = {}                                # slot -> generation of a clip the embedder is running on
+        self._jobs = []                                     # embedder calls in flight, oldest first: (event, slots, gens, out)
+        self._enroll_faults = set()                         # idle slots whose last capture the device aborted
+        self._enrolled = {}                                 # slot -> the embedding enrollment opened it with
+        self._epending = {}                                 # slot -> LH_ENROLL_* word for the next step
+        if n:
+            self._clips = torch.zeros(S, net.num_ch, net.stft_chunk_size * n, device=dev)
+            self._ewords = torch.zeros(3, S, dtype=torch.int32, device=dev)      # ecmd | estate: generation, chunks recorded
+            self._edone = net._host_words(S, dev)
+            self._edone_np = self._edone.numpy()
+            self._side = net._enroll_side(dev)
         self.graphs = None
         if use_graph:
             with torch.no_grad():
@@ -1081,6 +1164,9 @@ class SessionStreamer:
             cmd, active = self._words.data_ptr(), self._words[2].data_ptr()
             lib.call("lh_session_begin", ctypes.addressof(self._spans), len(self._spans), P(self.chunk_in), P(st.chunk), cmd,
                      active, S, stream)
+            if self.enroll_chunks:
+                lib.call("lh_session_capture", P(self.chunk_in), P(self._clips), P(self._ewords), P(self._ewords[1]),
+                         P(self._edone), self.enroll_chunks, S, stream)
             net._stream_chunk(st.chunk, st.gain, st.sets[k], st.sets[k ^ 1], st.rings, st.pos, st.out, st._pk, st._ws, None,
                               keep_nonfinite=1)
             lib.call("lh_ring_advance", P(st.pos), net.local_atten_len, stream)
@@ -1088,22 +1174,44 @@ class SessionStreamer:
                      P(st.out), cmd, active, P(self._fault), S, stream)
 
     def reset(self):
-        """Every slot idle, all state zero (what a new SessionStreamer starts from)."""
+        """Every slot idle, all state zero (what a new SessionStreamer starts from).  Captures and embeddings are cancelled."""
         self._st.reset()
         self._words.zero_()
         self._fault.zero_()
         self._gen = [0] * self.S
         self._pending.clear()
+        if self.enroll_chunks:
+            self._ewords.zero_()
+            self._edone.zero_()
+        self._capturing.clear()
+        self._embedding.clear()                             # calls in flight finish; their rows are dropped by generation
+        self._enroll_faults.clear()
+        self._enrolled.clear()
+        self._epending.clear()
 
     def _slot(self, slot: int) -> int:
         if not 0 <= slot < self.S:
             raise IndexError(f"slot {slot} out of range for {self.S} slots")
         return slot
 
+    def _new_gen(self) -> int:
+        gen = self._next_gen
+        self._next_gen = gen % self.GEN_MASK + 1
+        return gen
+
+    def _aborted(self) -> list:
+        """Capturing slots whose done word reports the abort of their current generation."""
+        d = self._edone_np
+        return [s for s, (g, _) in self._capturing.items() if int(d[s]) & 0xffffffff == g | self.ENROLL_FAULT]
+
     def faults(self) -> list:
-        """Slots the device closed (non-finite input, or an fp32 overflow inside the separator) since their last `open`."""
+        """Slots the device closed (non-finite input, or an fp32 overflow inside the separator) since their last `open`, and
+        idle slots whose enrollment capture it aborted (a non-finite recorded sample) since their last `enroll`."""
         f = self._fault_np
-        return [s for s, g in enumerate(self._gen) if g and int(f[s]) == g]
+        out = [s for s, g in enumerate(self._gen) if g and int(f[s]) == g]
+        if self._capturing or self._enroll_faults:
+            out = sorted(set(out) | self._enroll_faults | set(self._aborted()))
+        return out
 
     @property
     def active(self) -> list:
@@ -1111,31 +1219,81 @@ class SessionStreamer:
         f = self._fault_np
         return [s for s, g in enumerate(self._gen) if g and int(f[s]) != g]
 
+    @property
+    def enrolling(self) -> list:
+        """The slots whose clip is being recorded or embedded."""
+        bad = set(self._aborted()) if self._capturing else ()
+        return sorted(s for s in list(self._capturing) + list(self._embedding) if s not in bad)
+
+    def embedding_of(self, slot: int) -> torch.Tensor:
+        """The [256] device tensor `slot` was opened with by enrollment."""
+        self._slot(slot)
+        if slot not in self._enrolled:
+            raise ValueError(f"slot {slot} was not opened by enrollment")
+        return self._enrolled[slot]
+
     def _set_gain(self, slot: int, embed: torch.Tensor):
         st = self._st
         st.embed[slot].copy_(embed.reshape(-1), non_blocking=True)
         with torch.no_grad():                               # this row only, eager, stream-ordered before the next replay
             self.net._speaker_gain(st.embed[slot:slot + 1], st.gain_raw[slot:slot + 1], st.gain[slot:slot + 1])
 
-    def open(self, slot: int, embed: torch.Tensor):
-        """From the next `step` on `slot` is a fresh stream that listens for `embed` [256]."""
-        self._slot(slot)
-        if slot in self.active:
-            raise ValueError(f"slot {slot} is open: close() it first")
-        gen = self._next_gen
-        self._next_gen = gen % self.GEN_MASK + 1
+    def _open(self, slot: int, embed: torch.Tensor):
+        gen = self._new_gen()
         # the fault word of the previous listener holds an older generation: cleared for the host as of now, and on the
         # device by the chunk that opens the slot
         self._gen[slot] = gen
         self._pending[slot] = self.RESET | self.OPEN | (gen << self.GEN_SHIFT)
         self._set_gain(slot, embed)
 
-    def close(self, slot: int):
-        """From the next `step` on `slot` is idle: its output rows are exact zeros.  Also acknowledges a fault."""
+    def open(self, slot: int, embed: torch.Tensor):
+        """From the next `step` on `slot` is a fresh stream that listens for `embed` [256]."""
         self._slot(slot)
+        if slot in self.active:
+            raise ValueError(f"slot {slot} is open: close() it first")
+        if slot in self._capturing or slot in self._embedding:
+            self.poll()                                     # an aborted capture has left the slot idle
+            if slot in self._capturing or slot in self._embedding:
+                raise ValueError(f"slot {slot} is enrolling: close() it first")
+        self._enroll_faults.discard(slot)
+        self._enrolled.pop(slot, None)
+        self._open(slot, embed)
+
+    def enroll(self, slot: int, embedder):
+        """From the next `step` on the rows of idle `slot` are recorded, `enroll_chunks` of them; then
+        `embedder(clips [k, 2, 128 enroll_chunks]) -> [k, 256]` (an `EmbedTFGridNet` on this device) runs beside the chunk
+        loop and the slot opens on its row.  Until then the slot's output rows are zeros."""
+        self._slot(slot)
+        if not self.enroll_chunks:
+            raise ValueError("this SessionStreamer was built without enrollment: make_session_streamer(..., enroll_chunks=n)")
+        self.poll()
+        if slot in self.active:
+            raise ValueError(f"slot {slot} is open: close() it first")
+        if slot in self._capturing or slot in self._embedding:
+            raise ValueError(f"slot {slot} is enrolling already")
+        self._gen[slot] = 0                                 # a slot the device closed for a fault is idle there already
+        gen = self._new_gen()
+        self._enroll_faults.discard(slot)
+        self._enrolled.pop(slot, None)
+        self._capturing[slot] = (gen, embedder)
+        self._epending[slot] = self.ARM | (gen << self.GEN_SHIFT)
+
+    def close(self, slot: int):
+        """From the next `step` on `slot` is idle: its output rows are exact zeros.  Also acknowledges a fault, and cancels an
+        enrollment in progress: nothing opens later."""
+        self._slot(slot)
+        if slot in self._capturing or slot in self._embedding:
+            if self._capturing.pop(slot, None) is not None:
+                self._epending[slot] = self.CANCEL
+            self._embedding.pop(slot, None)                 # the call goes on; its row is dropped by generation
+            return
+        if slot in self._enroll_faults:
+            self._enroll_faults.discard(slot)
+            return
         if not self._gen[slot]:
             raise ValueError(f"slot {slot} is not open")
         self._gen[slot] = 0
+        self._enrolled.pop(slot, None)
         self._pending[slot] = self.RESET | self.CLOSE
 
     def set_embedding(self, slot: int, embed: torch.Tensor):
@@ -1145,12 +1303,44 @@ class SessionStreamer:
             raise ValueError(f"slot {slot} is not open")
         self._set_gain(slot, embed)
 
+    def poll(self):
+        """Moves enrollments on, without waiting for the device: clips the device has completed go to the embedder on the side
+        stream, finished embeddings open their slots.  `step` calls it first; call it more often if you like."""
+        if not self._capturing and not self._jobs:
+            return
+        d, ready = self._edone_np, {}
+        for s in sorted(self._capturing):
+            g, embedder = self._capturing[s]
+            w = int(d[s]) & 0xffffffff
+            if w == g:
+                ready.setdefault(embedder, []).append(s)
+            elif w == g | self.ENROLL_FAULT:
+                del self._capturing[s]
+                self._enroll_faults.add(s)
+        for embedder, slots in ready.items():               # one call per embedder: a batch in ascending slot order
+            gens = [self._capturing.pop(s)[0] for s in slots]
+            # views and a copy on the side stream: nothing here moves host memory, so nothing waits
+            clips = lambda: self._clips[slots[0]:slots[0] + 1] if len(slots) == 1 else torch.stack([self._clips[s] for s in slots])
+            with torch.no_grad():
+                out, done = self._side.run(lambda: embedder(clips()))
+            self._embedding.update(zip(slots, gens))
+            self._jobs.append((done, slots, gens, out))
+        while self._jobs and self._side.finished(self._jobs[0][0]):      # one stream: the calls finish in order
+            done, slots, gens, out = self._jobs.pop(0)
+            self._side.hand_over(done, out)
+            for i, s in enumerate(slots):
+                if self._embedding.get(s) == gens[i]:       # else: cancelled (and perhaps enrolling again) meanwhile
+                    del self._embedding[s]
+                    self._enrolled[s] = out[i]
+                    self._open(s, out[i])
+
     def step(self, chunks: torch.Tensor) -> torch.Tensor:
         """chunks [S, 2, 192] (rows of idle slots are ignored) -> [S, 2, 128] (rows of idle slots are zeros); a view the next
         `step` overwrites.  Never raises for a slot's fault: see `faults()`."""
         st = self._st
         st._check_repacked()
         st._check_versions()
+        self.poll()
         if self._pending:
             # a FRESH pinned array per batch of commands: the host allocator hands its memory out again only after the
             # copy below has run, so a host that runs ahead of the device cannot overwrite commands in flight
@@ -1160,6 +1350,13 @@ class SessionStreamer:
                 words[slot] = w
             self._pending.clear()
             self._words[0].copy_(src, non_blocking=True)
+        if self._epending:                                  # the LH_ENROLL_* words travel the same way
+            src = self.net._host_words(self.S, self.device)
+            words = src.numpy()
+            for slot, w in self._epending.items():
+                words[slot] = w
+            self._epending.clear()
+            self._ewords[0].copy_(src, non_blocking=True)
         self.chunk_in.copy_(chunks)
         with torch.no_grad():
             if self.graphs is not None:

@@ -6,6 +6,12 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
     python scripts/bench_sessions.py [--batches 1,64] [--steps 625] [--warmup 100] [--out profiles/xyz.json]
     python scripts/bench_sessions.py --trace idle|reset --batches 8     # a short loop for rocprofv3 --kernel-trace --stats:
         idle = every slot open, nothing pending; reset = one close + one open pending in EVERY chunk
+    python scripts/bench_sessions.py --enroll [--batches 1,64] [--enroll-chunks 625] [--out profiles/xyz.txt]
+        what enrollment costs the chunk loop, in DEVICE time per chunk (HIP events around every replay on the loop's stream:
+        `step` returns without waiting, a host timer would record the enqueue): (a) the capture node with nothing enrolling
+        against a streamer built without it, interleaved in one run; (b) the chunks that overlap a running embedder call, one
+        and four slots embedding, side stream at default and at lowest priority; (c) steps from the capture's last chunk to
+        the slot's appearance in `active`.  The loop waits for every chunk's end event, as a real-time consumer does.
 """
 import argparse
 import json
@@ -44,8 +50,115 @@ def timed(step, chunks, steps, warmup, before=None):
             "max_ms": lat[-1] * 1e3}
 
 
+def pct(v, q):
+    v = sorted(v)
+    return v[min(len(v) - 1, int(len(v) * q))]
+
+
+def dev_steps(ss, chunks, i0, n, before=None, until=None):
+    """n steps (or until `until()` after a step) with events around each on the loop's stream -> [(start, end)] events."""
+    evs = []
+    for i in range(i0, i0 + n):
+        if before is not None:
+            before(i)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ss.step(chunks[i % len(chunks)])
+        e1.record()
+        e1.synchronize()
+        evs.append((e0, e1))
+        if until is not None and until():
+            break
+    return evs
+
+
+def stats(ms):
+    return {"n": len(ms), "p50_ms": pct(ms, 0.5), "p99_ms": pct(ms, 0.99), "max_ms": max(ms)}
+
+
+def enroll_bench(net, args):
+    from lookoncetohear_amd.embed_net import EmbedTFGridNet
+    emb_net = EmbedTFGridNet(**config.EMBED_PARAMS).eval()
+    emb_net.load_state_dict(config.embedder_weights(0), strict=True)
+    emb_net = emb_net.to(DEV)
+    n_en = args.enroll_chunks
+    with torch.no_grad():
+        for k in (1, 4):
+            emb_net(torch.zeros(k, 2, 128 * n_en, device=DEV))       # packs the weights, fills the allocator's pools
+    torch.cuda.synchronize()
+    lines = [f"enrollment cost, device time per chunk (HIP events around each replay), enroll_chunks = {n_en}, "
+             f"{args.steps} steps per block after {args.warmup} warm-up"]
+    for B in [int(b) for b in args.batches.split(",")]:
+        d = synth.batch(list(range(B)), 80000)
+        mix = torch.nn.functional.pad(d["mixture"], (0, 64)).to(DEV)
+        emb = d["embedding_gt"][:, 0].to(DEV)
+        chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+        # ---- (a) the capture node, nothing enrolling: blocks of the two streamers interleaved
+        pair = {"without": net.make_session_streamer(B, DEV), "with": net.make_session_streamer(B, DEV, enroll_chunks=n_en)}
+        ms = {k: [] for k in pair}
+        for ss in pair.values():
+            for s in range(B):
+                ss.open(s, emb[s])
+            dev_steps(ss, chunks, 0, args.warmup)
+        for rep in range(4):
+            for k, ss in pair.items():
+                ms[k] += [a.elapsed_time(b) for a, b in dev_steps(ss, chunks, 0, args.steps // 4)]
+        ra, rb = stats(ms["without"]), stats(ms["with"])
+        lines.append(f"(a) S={B:3d} capture node idle   without: p50 {ra['p50_ms']:.4f} p99 {ra['p99_ms']:.4f} ms   with: p50 "
+                     f"{rb['p50_ms']:.4f} p99 {rb['p99_ms']:.4f} ms   p50 cost {1e3 * (rb['p50_ms'] - ra['p50_ms']):+.1f} us")
+        del pair
+        # ---- (b), (c): k slots enroll at once (the others are open), at both priorities of the side stream
+        for k in ([1] if B == 1 else [1, 4]):
+            for low in (False, True):
+                net.enroll_low_priority = low
+                ss = net.make_session_streamer(B, DEV, enroll_chunks=n_en)
+                net.enroll_low_priority = False
+                for s in range(k, B):
+                    ss.open(s, emb[s])
+                dev_steps(ss, chunks, 0, args.warmup)
+                spans = []
+
+                def embedder(x):
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    out = emb_net(x)
+                    t1.record()
+                    spans.append((t0, t1, x.shape[0]))
+                    return out
+                for s in range(k):
+                    ss.enroll(s, embedder)
+                evs = dev_steps(ss, chunks, 0, n_en)                 # the capture: its last chunk is evs[-1]
+                base = [a.elapsed_time(b) for a, b in evs[n_en // 2:]]
+                tail = dev_steps(ss, chunks, n_en, 2000, until=lambda: len(ss.active) == B)
+                opened_after = len(tail)
+                tail += dev_steps(ss, chunks, n_en + len(tail), 20)
+                torch.cuda.synchronize()
+                assert ss.faults() == [] and len(ss.active) == B and len(spans) == 1 and spans[0][2] == k
+                ref = evs[0][0]
+                t0, t1 = ref.elapsed_time(spans[0][0]), ref.elapsed_time(spans[0][1])
+                over = [a.elapsed_time(b) for a, b in tail if ref.elapsed_time(b) > t0 and ref.elapsed_time(a) < t1]
+                assert over, "no chunk overlapped the embedder call"
+                ro, rn = stats(over), stats(base)
+                worst = ro["max_ms"]
+                lines.append(f"(b) S={B:3d} {k} embedding, side stream {'lowest ' if low else 'default'} priority: embedder "
+                             f"{t1 - t0:.3f} ms, {ro['n']} chunks overlap it: p50 {ro['p50_ms']:.4f} p99 {ro['p99_ms']:.4f} max "
+                             f"{ro['max_ms']:.4f} ms   (capturing, no embedder: p50 {rn['p50_ms']:.4f} p99 {rn['p99_ms']:.4f} max "
+                             f"{rn['max_ms']:.4f} ms)   {'BELOW' if worst < 8.0 else 'NOT below'} the 8 ms chunk period")
+                lines.append(f"(c) S={B:3d} {k} embedding, {'lowest ' if low else 'default'}: in `active` {opened_after} steps after the "
+                             f"capture's last chunk (this loop runs chunks back to back; at one step per 8 ms: "
+                             f"{1 + int((t1 - t0) // 8.0) + 1} steps)")
+                del ss
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--enroll", action="store_true")
+    ap.add_argument("--enroll-chunks", type=int, default=625)
     ap.add_argument("--batches", default="1,64")
     ap.add_argument("--steps", type=int, default=625)
     ap.add_argument("--warmup", type=int, default=100)
@@ -56,6 +169,8 @@ def main():
     net = Net(**config.TSH_PARAMS).eval()
     net.load_state_dict(config.separator_weights(0), strict=True)
     net = net.to(DEV)
+    if args.enroll:
+        return enroll_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
