@@ -136,49 +136,23 @@ def _axis_path(cfg, p, pre, ax, x):
                                stride=cfg.hs)                              # [N, C, L]
 
 
-def block(cfg: ECfg, p: dict, pre: str, x, taps=None):
-    B, C, T, Q = x.shape
-    assert (T - cfg.ks) % cfg.hs == 0 and (Q - cfg.ks) % cfg.hs == 0       # hs = 1: no padding branch
-    y = _ln4d(x, p[pre + "intra_norm.gamma"], p[pre + "intra_norm.beta"], cfg.eps)
-    y = _axis_path(cfg, p, pre, "intra", y.transpose(1, 2).reshape(B * T, C, Q)).view(B, T, C, Q).transpose(1, 2)
-    x1 = y + x
-    if taps is not None:
-        taps[pre + 'x1'] = x1.permute(0, 2, 3, 1)
-    y = _ln4d(x1, p[pre + "inter_norm.gamma"], p[pre + "inter_norm.beta"], cfg.eps)
-    y = _axis_path(cfg, p, pre, "inter", y.permute(0, 3, 1, 2).reshape(B * Q, C, T)).view(B, Q, C, T).permute(0, 2, 3, 1)
-    x2 = y + x1
-    if taps is not None:
-        taps[pre + 'x2'] = x2.permute(0, 2, 3, 1)
-
-    def head(nm, h):
-        q = pre + f"attn_conv_{nm}_{h}."
-        z = TF.conv2d(x2, p[q + "0.weight"], p[q + "0.bias"])
-        return _ln4dcf(_prelu(z, p[q + "1.weight"]), p[q + "2.gamma"], p[q + "2.beta"], cfg.eps)
-
-    Qh = torch.cat([head("Q", h) for h in range(cfg.nh)], 0)               # [nh*B, E, T, F] (head-major)
-    Kh = torch.cat([head("K", h) for h in range(cfg.nh)], 0)
-    Vh = torch.cat([head("V", h) for h in range(cfg.nh)], 0)               # [nh*B, Vd, T, F]
-    Qf = Qh.transpose(1, 2).flatten(2)                                     # [nh*B, T, E*F]  (e-major, f-minor)
-    Kf = Kh.transpose(1, 2).flatten(2)
-    Vt = Vh.transpose(1, 2)
-    att = torch.softmax(Qf @ Kf.transpose(1, 2) / math.sqrt(Qf.shape[-1]), dim=2)     # full T x T, no mask
-    O = (att @ Vt.flatten(2)).reshape(Vt.shape).transpose(1, 2)            # [nh*B, Vd, T, F]
-    O = O.view(cfg.nh, B, cfg.Vd, T, Q).transpose(0, 1).reshape(B, cfg.nh * cfg.Vd, T, Q)
-    if taps is not None:
-        taps[pre + 'Q'], taps[pre + 'K'], taps[pre + 'V'] = Qh, Kh, Vh        # [nh*B, d, T, F], head-major batch
-        taps[pre + 'O'] = O.permute(0, 2, 3, 1)                               # [B, T, F, 64]
-    q = pre + "attn_concat_proj."
-    z = _prelu(TF.conv2d(O, p[q + "0.weight"], p[q + "0.bias"]), p[q + "1.weight"])
-    return _ln4dcf(z, p[q + "2.gamma"], p[q + "2.beta"], cfg.eps) + x2
+def ln_channels(x, eps=1e-5):
+    """Channel LayerNorm without affine, x [..., C] channel-last: the value the kernels' split images hold."""
+    mu = x.mean(-1, keepdim=True)
+    var = x.var(-1, unbiased=False, keepdim=True)
+    return (x - mu) / torch.sqrt(var + eps)
 
 
-def forward(cfg: ECfg, sd: dict, x, dtype=torch.float32, taps=None):
-    """EmbedTFGridNet.forward (tfgridnet_orig/tfgridnet.py:100-127): x [B, M, N] -> [B, embed_dim]."""
-    p = {k: v.detach().to("cpu", dtype) for k, v in sd.items()}
-    x = x.detach().to("cpu", dtype).transpose(1, 2)                        # [B, N, M]
-    x = x / torch.std(x, dim=(1, 2), keepdim=True)                         # unbiased std, :109-110
+# ---- stages: each takes and returns tensors on the caller's device and dtype (p = parameters already there);
+# block() and forward() below are their composition
+
+def front_end(cfg: ECfg, p: dict, x, taps=None):
+    """x [B, M, N] -> (z [B, C, T, F], inv_std [B]): x / std(x) (unbiased), STFT, re/im stacking, Conv2d 3x3, GroupNorm(1, C)."""
+    x = x.transpose(1, 2)                                                  # [B, N, M]
+    std = torch.std(x, dim=(1, 2), keepdim=True)                           # unbiased std, :109-110
+    x = x / std
     B, N, M = x.shape
-    win = torch.hann_window(cfg.nfft, dtype=dtype)                         # espnet2 Stft: hann, center, reflect pad
+    win = torch.hann_window(cfg.nfft, dtype=x.dtype, device=x.device)      # espnet2 Stft: hann, center, reflect pad
     spec = torch.stft(x.transpose(1, 2).reshape(B * M, N), cfg.nfft, cfg.hop, cfg.nfft, win, center=True,
                       pad_mode="reflect", normalized=False, onesided=True, return_complex=True)   # [B*M, F, T]
     spec = spec.view(B, M, cfg.F, -1).permute(0, 1, 3, 2)                  # [B, M, T, F]
@@ -188,14 +162,87 @@ def forward(cfg: ECfg, sd: dict, x, dtype=torch.float32, taps=None):
         taps['spec'] = torch.cat([spec.real, spec.imag], dim=1)
         taps['zraw'] = z.permute(0, 2, 3, 1)
     z = TF.group_norm(z, 1, p["conv.1.weight"], p["conv.1.bias"], cfg.eps)
+    return z, (1.0 / std).reshape(B)
+
+
+def axis(cfg: ECfg, p: dict, pre: str, ax: str, x):
+    """One axis path of a block, x [B, C, T, F] -> same shape: channel LayerNorm, unfold, BiLSTM, ConvTranspose1d, + x.
+    ax = "intra": sequences are frames, scanned over frequency; "inter": sequences are bins, scanned over time."""
+    B, C, T, Q = x.shape
+    assert (T - cfg.ks) % cfg.hs == 0 and (Q - cfg.ks) % cfg.hs == 0       # hs = 1: no padding branch
+    y = _ln4d(x, p[pre + f"{ax}_norm.gamma"], p[pre + f"{ax}_norm.beta"], cfg.eps)
+    if ax == "intra":
+        y = _axis_path(cfg, p, pre, "intra", y.transpose(1, 2).reshape(B * T, C, Q)).view(B, T, C, Q).transpose(1, 2)
+    else:
+        y = _axis_path(cfg, p, pre, "inter", y.permute(0, 3, 1, 2).reshape(B * Q, C, T)).view(B, Q, C, T).permute(0, 2, 3, 1)
+    return y + x
+
+
+def qkv_heads(cfg: ECfg, p: dict, pre: str, x2):
+    """x2 [B, C, T, F] -> Q, K [nh*B, E, T, F] and V [nh*B, Vd, T, F], head-major batch: 1x1 conv, PReLU, LayerNorm over (C, F)."""
+    def head(nm, h):
+        q = pre + f"attn_conv_{nm}_{h}."
+        z = TF.conv2d(x2, p[q + "0.weight"], p[q + "0.bias"])
+        return _ln4dcf(_prelu(z, p[q + "1.weight"]), p[q + "2.gamma"], p[q + "2.beta"], cfg.eps)
+
+    Qh = torch.cat([head("Q", h) for h in range(cfg.nh)], 0)               # [nh*B, E, T, F] (head-major)
+    Kh = torch.cat([head("K", h) for h in range(cfg.nh)], 0)
+    Vh = torch.cat([head("V", h) for h in range(cfg.nh)], 0)               # [nh*B, Vd, T, F]
+    return Qh, Kh, Vh
+
+
+def attention(cfg: ECfg, Qh, Kh, Vh):
+    """Full T x T attention per (head, utterance): (scaled scores [nh*B, T, T], softmax [nh*B, T, T], merged O [B, C, T, F])."""
+    B, T, Q = Qh.shape[0] // cfg.nh, Qh.shape[2], Qh.shape[3]
+    Qf = Qh.transpose(1, 2).flatten(2)                                     # [nh*B, T, E*F]  (e-major, f-minor)
+    Kf = Kh.transpose(1, 2).flatten(2)
+    Vt = Vh.transpose(1, 2)
+    sc = Qf @ Kf.transpose(1, 2) / math.sqrt(Qf.shape[-1])
+    att = torch.softmax(sc, dim=2)                                         # full T x T, no mask
+    O = (att @ Vt.flatten(2)).reshape(Vt.shape).transpose(1, 2)            # [nh*B, Vd, T, F]
+    O = O.view(cfg.nh, B, cfg.Vd, T, Q).transpose(0, 1).reshape(B, cfg.nh * cfg.Vd, T, Q)
+    return sc, att, O
+
+
+def concat_proj_ln_res(cfg: ECfg, p: dict, pre: str, O, x2):
+    """O, x2 [B, C, T, F] -> the block's output: 1x1 conv, PReLU, LayerNorm over (C, F), + x2."""
+    q = pre + "attn_concat_proj."
+    z = _prelu(TF.conv2d(O, p[q + "0.weight"], p[q + "0.bias"]), p[q + "1.weight"])
+    return _ln4dcf(z, p[q + "2.gamma"], p[q + "2.beta"], cfg.eps) + x2
+
+
+def head(cfg: ECfg, p: dict, z):
+    """z [B, C, T, F] -> [B, embed_dim]: Linear over (c-major) C*F per frame, LayerNorm, mean over frames."""
+    B, T = z.shape[0], z.shape[2]
+    e = z.permute(0, 2, 1, 3).reshape(B, T, cfg.C * cfg.F)                 # [B, T, C*F] (c-major)
+    e = e @ p["embed_proj.0.weight"].t() + p["embed_proj.0.bias"]
+    e = TF.layer_norm(e, (cfg.embed_dim,), p["embed_proj.1.weight"], p["embed_proj.1.bias"], cfg.eps)
+    return e.mean(1)
+
+
+def block(cfg: ECfg, p: dict, pre: str, x, taps=None):
+    x1 = axis(cfg, p, pre, "intra", x)
+    if taps is not None:
+        taps[pre + 'x1'] = x1.permute(0, 2, 3, 1)
+    x2 = axis(cfg, p, pre, "inter", x1)
+    if taps is not None:
+        taps[pre + 'x2'] = x2.permute(0, 2, 3, 1)
+    Qh, Kh, Vh = qkv_heads(cfg, p, pre, x2)
+    _, _, O = attention(cfg, Qh, Kh, Vh)
+    if taps is not None:
+        taps[pre + 'Q'], taps[pre + 'K'], taps[pre + 'V'] = Qh, Kh, Vh        # [nh*B, d, T, F], head-major batch
+        taps[pre + 'O'] = O.permute(0, 2, 3, 1)                               # [B, T, F, 64]
+    return concat_proj_ln_res(cfg, p, pre, O, x2)
+
+
+def forward(cfg: ECfg, sd: dict, x, dtype=torch.float32, taps=None):
+    """EmbedTFGridNet.forward (tfgridnet_orig/tfgridnet.py:100-127): x [B, M, N] -> [B, embed_dim]."""
+    p = {k: v.detach().to("cpu", dtype) for k, v in sd.items()}
+    z, _ = front_end(cfg, p, x.detach().to("cpu", dtype), taps)
     if taps is not None:
         taps['z0'] = z.permute(0, 2, 3, 1)
     for i in range(cfg.nblk):
         z = block(cfg, p, f"blocks.{i}.", z, taps)
         if taps is not None:
             taps[f'blocks.{i}.out'] = z.permute(0, 2, 3, 1)
-    T = z.shape[2]
-    e = z.permute(0, 2, 1, 3).reshape(B, T, cfg.C * cfg.F)                 # [B, T, C*F] (c-major)
-    e = e @ p["embed_proj.0.weight"].t() + p["embed_proj.0.bias"]
-    e = TF.layer_norm(e, (cfg.embed_dim,), p["embed_proj.1.weight"], p["embed_proj.1.bias"], cfg.eps)
-    return e.mean(1)
+    return head(cfg, p, z)
