@@ -466,7 +466,7 @@ int lh_metric_sums(const float* outputs, const float* target, const float* mixtu
 int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B, int n_samples,
                      int sr, int frame, double rms_threshold, lh_stream_t stream);
 
-/* ---- streaming sessions (ABI 16, 17) ----------------------------------------------------------------------------------------
+/* ---- streaming sessions (ABI 16 - 18) ----------------------------------------------------------------------------------------
  * A batched streaming host serves S listener SLOTS in lock-step (one 8 ms chunk of every slot per step; slot = batch row of
  * every streaming entry point above).  These two launches bracket the chunk's launch sequence — first and last node of a
  * captured per-chunk graph — and let slots open, close and fail one at a time, on the device and without a host wait (the
@@ -507,6 +507,40 @@ int lh_session_begin(const lh_span_t* spans, int n_spans, const float* chunk_in,
                      const unsigned* active, int S, lh_stream_t stream);
 int lh_session_end(const lh_span_t* spans, int n_spans, const float* chunk_in, float* out, unsigned* cmd, unsigned* active,
                    unsigned* fault, int S, lh_stream_t stream);
+
+/* Row compaction (ABI 18): a host that is rarely full keeps its open listeners in the leading ROWS of the same buffers and
+ * launches every kernel of the chunk for n_rows <= S of them.  SLOT stays the listener's number towards the clients (chunk_in,
+ * out, fault, the enrollment words); ROW is the batch row of every streaming entry point, of the spans, of chunk and of the
+ * words cmd [2][S] / active [S], whose stride stays S.  Call order of one chunk, all with the same n_rows:
+ *   lh_session_move -> lh_session_begin_rows -> (lh_session_capture, by slot, S) -> the chunk's launches with B = n_rows ->
+ *   lh_ring_advance -> lh_session_end_rows.
+ *   from       [S] device words, the move table: from[d] = r + 1 copies row r over row d, 0 = nothing.  Posted by the host with
+ *              the other tables (one asynchronous copy ahead of the step), read by lh_session_move for d < n_rows, zeroed by
+ *              lh_session_end_rows — a replay without a new table moves nothing.  The pairs of one launch must be disjoint:
+ *              every source above, every destination below the host's new row count.
+ *   slot_of    [S] row -> slot, negative = the row has no listener: it is idle whatever its words say (as if the host had
+ *              posted CLOSE; a RESET the device posted on it is still served), reads no input and reports nothing
+ *   row_of     [S] slot -> row, negative = none
+ *   lh_session_move       (grid over row x tile; spans = lh_session_begin's table plus the speaker gain) copies the row's slice
+ *              of every span with 16-byte loads and stores, active[r] -> active[d] and cmd[1][r] -> cmd[1][d].  Bytes, not
+ *              numbers: a moved listener keeps its bits.  The source row is not cleared: the host takes its slot away
+ *              (slot_of) or opens it for the next listener (OPEN comes with RESET).
+ *   lh_session_begin_rows lh_session_begin for row r: decides from cmd[.][r], active[r] and chunk_in[slot_of[r]], writes
+ *              chunk[r] and zeroes row r's slice of every span
+ *   lh_session_end_rows   lh_session_end for row r (spans: the (h, c) just written): reads out_rows[r], writes it, or zeros, to
+ *              out[slot_of[r]], fault[slot_of[r]], the words of row r, from[r] = 0 (from may be null); one more workgroup
+ *              zeroes out[s] of every slot whose row_of[s] is not in [0, n_rows).  out_rows [S][2][128] is what
+ *              lh_deconv_istft wrote, out [S][2][128] what the clients get.
+ * A fault the host has not seen yet may travel with a move: the moved `active` word is then 0 and a pending RESET moves along,
+ * so the row is idle and clean in its new place and the fault stays reported under the slot with its generation.
+ * LH_ERR_ARG: as above, and n_rows outside [1, S], out_rows == out.  None of the three allocates or synchronises. */
+int lh_session_move(const lh_span_t* spans, int n_spans, const int* from, unsigned* cmd, unsigned* active, int n_rows, int S,
+                    lh_stream_t stream);
+int lh_session_begin_rows(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk, const unsigned* cmd,
+                          const unsigned* active, const int* slot_of, int n_rows, int S, lh_stream_t stream);
+int lh_session_end_rows(const lh_span_t* spans, int n_spans, const float* chunk_in, const float* out_rows, float* out,
+                        unsigned* cmd, unsigned* active, unsigned* fault, const int* slot_of, const int* row_of, int* from,
+                        int n_rows, int S, lh_stream_t stream);
 
 /* Enrollment capture (ABI 17): "look once" from the listener's own stream.  One more node of the per-chunk graph, right after
  * lh_session_begin, in a host built for enrollment: an ARMED slot's next n_chunks input rows are recorded on the device, and a

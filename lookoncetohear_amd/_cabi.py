@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -38,6 +38,10 @@ SIGNATURES = {
     "lh_session_end": [_P, _I, _P, _P, _P, _P, _P, _I, _P],
     # enrollment capture (ABI 17): the node after lh_session_begin in a SessionStreamer built with enroll_chunks
     "lh_session_capture": [_P] * 5 + [_I, _I, _P],
+    # row compaction (ABI 18): the moves and the row forms of the two bracket nodes, SessionStreamer(compact=True)
+    "lh_session_move": [_P, _I, _P, _P, _P, _I, _I, _P],
+    "lh_session_begin_rows": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],
+    "lh_session_end_rows": [_P, _I] + [_P] * 9 + [_I, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)

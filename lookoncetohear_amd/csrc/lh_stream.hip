@@ -216,12 +216,14 @@ __global__ void __launch_bounds__(IS_NT) k_inter_matvec(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Streaming sessions (include/lookonce_hip.h, ABI 16): the first and the last node of a batched streamer's per-chunk graph.
+// Streaming sessions (include/lookonce_hip.h, ABI 16; row forms and moves: ABI 18): the first and the last node of a batched streamer's per-chunk graph.
 // Slots (batch rows) open, close and fail one at a time while the chunk loop goes on in lock-step.  Plain streaming
 // kernels: a few word loads and the slot's 1.5 KB input row per wave to decide, 16-byte stores to zero a slot's state.
 // Who writes what: k_session_begin writes the gated input and the state it zeroes, never a word, so every workgroup of a
 // slot reaches the same decision from the same unmodified inputs; k_session_end (one workgroup per slot, after every other
-// kernel of the chunk) repeats that decision and is the only writer of cmd / active / fault.
+// kernel of the chunk) repeats that decision and is the only writer of cmd / active / fault.  A compacting host (ABI 18) has one
+// more writer, BEFORE both: k_session_move copies a moved row's `active` and device command word with the row, and the two
+// kernels then decide from the moved words.
 // ------------------------------------------------------------------------------------------------------
 struct SessSpans { lh_span_t s[LH_SESSION_MAX_SPANS]; int n; };     // travels in the kernel arguments
 constexpr int SS_NT = 256;
@@ -246,10 +248,11 @@ struct SessLoads { unsigned host, dev, act; float4 x0, x1; };
 // Both kernels are latency: a handful of dependent memory round trips at ~1-2 us each is all they cost when nothing happens.
 // So everything a decision needs is REQUESTED AT ONCE and unconditionally — the three words and the wave's two float4 of the
 // slot's input row — and only then looked at.
+// `s` indexes the words, `in_row` the input rows: the same number in the lock-step kernels, row and slot in the row forms.
 __device__ __forceinline__ SessLoads sess_load(const float* __restrict__ chunk_in, const unsigned* cmd, const unsigned* active,
-                                               int S, int s, int lane) {
+                                               int S, int s, int in_row, int lane) {
     SessLoads l;
-    const float4* in4 = reinterpret_cast<const float4*>(chunk_in + (long)s * NMIC * NFFT);
+    const float4* in4 = reinterpret_cast<const float4*>(chunk_in + (long)in_row * NMIC * NFFT);
     l.host = cmd[s];
     l.dev = cmd[S + s];
     l.act = active[s];
@@ -278,7 +281,7 @@ __global__ void __launch_bounds__(SS_NT) k_session_begin(SessSpans sp, const flo
                                                          float* __restrict__ chunk, const unsigned* __restrict__ cmd,
                                                          const unsigned* __restrict__ active, int S) {
     const int tid = threadIdx.x, s = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, tid & 63);
+    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, s, tid & 63);
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     const long o = (long)s * SS_IN4 + min(tid, SS_IN4 - 1);
     const float4 mine = reinterpret_cast<const float4*>(chunk_in)[o];
@@ -302,7 +305,7 @@ __global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, const float
                                                        unsigned* cmd, unsigned* active, unsigned* fault, int S) {
     __shared__ int wbad[SE_NT / 64];
     const int tid = threadIdx.x, lane = tid & 63, s = blockIdx.x;
-    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, lane);
+    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, s, lane);
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     float4* o4 = reinterpret_cast<float4*>(out) + (long)s * SS_OUT4;
     const float4 ov = o4[tid & (SS_OUT4 - 1)];
@@ -345,6 +348,139 @@ __global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, const float
         else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[s], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         cmd[s] = 0u;
         cmd[S + s] = overflow ? (unsigned)LH_SESSION_RESET : 0u;
+    }
+}
+
+// Row forms (ABI 18): the words, the gated chunk and the state belong to ROW r of a compacting host, the input row to the
+// listener's SLOT slot_of[r].  A row without a slot (< 0, or not a slot) decides as if the host had posted CLOSE: it is idle
+// whatever its words say, and a RESET the device posted on it is still served.
+struct SessRow { int slot; bool owned; };
+__device__ __forceinline__ SessRow sess_row(const int* __restrict__ slot_of, int r, int S) {
+    const int slot = slot_of[r];
+    const bool owned = slot >= 0 && slot < S;
+    return SessRow{owned ? slot : 0, owned};
+}
+
+// grid (tiles, rows launched), block 256; the words keep their stride S.  k_session_begin with one more dependent load
+__global__ void __launch_bounds__(SS_NT) k_session_begin_rows(SessSpans sp, const float* __restrict__ chunk_in,
+                                                              float* __restrict__ chunk, const unsigned* __restrict__ cmd,
+                                                              const unsigned* __restrict__ active,
+                                                              const int* __restrict__ slot_of, int S) {
+    const int tid = threadIdx.x, r = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const SessRow w = sess_row(slot_of, r, S);
+    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, tid & 63);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[(long)w.slot * SS_IN4 + min(tid, SS_IN4 - 1)];
+    if (!w.owned) l.host = LH_SESSION_CLOSE;
+    const SessDecision d = sess_decide(l);
+    if (tile == 0 && tid < SS_IN4)                 // gather and gate: chunk[row] = chunk_in[slot] of a live listener
+        reinterpret_cast<float4*>(chunk)[(long)r * SS_IN4 + tid] = d.live ? mine : z;
+    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
+    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the row's slice of every state tensor
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        float4* p = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)r * sp.s[i].bytes);
+        const long hi = n16 * (tile + 1) / ntile;
+        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) p[j] = z;
+    }
+}
+
+// grid rows launched + 1, block 1024.  Workgroup r < n_rows is ROW r: k_session_end's scan of the row's output and fresh
+// (h, c), then it scatters the row's output, or zeros, to out[slot_of[r]], reports under the SLOT's number and takes the
+// row's entry out of the move table.  The workgroup after the last row silences every slot that has no row among those
+// launched, so every row of `out` is written in every chunk.
+__global__ void __launch_bounds__(SE_NT) k_session_end_rows(SessSpans sp, const float* __restrict__ chunk_in,
+                                                            const float* __restrict__ out_rows, float* __restrict__ out,
+                                                            unsigned* cmd, unsigned* active, unsigned* fault,
+                                                            const int* __restrict__ slot_of, const int* __restrict__ row_of,
+                                                            int* from, int n_rows, int S) {
+    __shared__ int wbad[SE_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, r = blockIdx.x;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r >= n_rows) {                             // the whole workgroup: 16 slots of 64 float4 per pass
+        for (int q = tid >> 6; q < S; q += SE_NT / 64) {
+            const int qr = row_of[q];
+            if (qr < 0 || qr >= n_rows) reinterpret_cast<float4*>(out)[(long)q * SS_OUT4 + lane] = z;
+        }
+        return;
+    }
+    const SessRow w = sess_row(slot_of, r, S);
+    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, lane);
+    const float4 ov = reinterpret_cast<const float4*>(out_rows)[(long)r * SS_OUT4 + (tid & (SS_OUT4 - 1))];
+    float4 v[SE_SP][SE_U];                         // branch-free, all requested before any is looked at (k_session_end)
+#pragma unroll
+    for (int i = 0; i < SE_SP; ++i) {
+        const lh_span_t sq = sp.s[i < sp.n ? i : 0];
+        const int last = (int)min((long)(sq.bytes >> 4), (long)SE_U * SE_NT) - 1;
+        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)r * sq.bytes);
+#pragma unroll
+        for (int u = 0; u < SE_U; ++u) v[i][u] = p[min(tid + u * SE_NT, last)];
+    }
+    bool bad = nonfinite4(ov);
+#pragma unroll
+    for (int i = 0; i < SE_SP; ++i)
+#pragma unroll
+        for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
+    for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
+                                                          (unsigned long long)r * sp.s[i].bytes);
+        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(p[j]);
+    }
+    if (!w.owned) l.host = LH_SESSION_CLOSE;
+    const SessDecision d = sess_decide(l);
+    bad = wave_any(bad);
+    if (lane == 0) wbad[tid >> 6] = bad ? 1 : 0;
+    __syncthreads();                               // also: every wave has read the words thread 0 is about to write
+    int any = 0;
+#pragma unroll
+    for (int q = 0; q < SE_NT / 64; ++q) any |= wbad[q];
+    const bool overflow = d.live && any != 0;
+    const bool on = d.live && !overflow;
+    if (w.owned && tid < SS_OUT4) reinterpret_cast<float4*>(out)[(long)w.slot * SS_OUT4 + tid] = on ? ov : z;
+    if (tid == 0) {
+        active[r] = on ? d.gen : 0u;
+        if (w.owned) {                             // an unowned row is idle: nothing to report
+            if (d.bad_in || overflow) __hip_atomic_store(&fault[w.slot], d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[w.slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        cmd[r] = 0u;
+        cmd[S + r] = overflow ? (unsigned)LH_SESSION_RESET : 0u;
+        if (from) from[r] = 0;
+    }
+}
+
+// Row moves (ABI 18): the first node of a compacting host's chunk.  from[d] = r + 1 copies row r over row d — the row's slice
+// of every span (the state of lh_session_begin's table and the speaker gain), its `active` word and the command word the
+// device posted on it: everything a row owns but the host's command word, which the host addresses to the row's new place
+// itself.  Bytes, not numbers: 16-byte loads and stores, a thread's SM_U loads requested together before it stores any.  The
+// host hands out disjoint pairs (every source lies above, every destination below the new row count), so the workgroups of
+// one launch share nothing; a row without an entry costs its workgroups one word load.  lh_session_end_rows zeroes the
+// entries afterwards: the table is read-only here, and a replay without a new table moves nothing.
+constexpr int SM_U = 4;
+__global__ void __launch_bounds__(SS_NT) k_session_move(SessSpans sp, const int* __restrict__ from, unsigned* cmd,
+                                                        unsigned* active, int S) {
+    const int tid = threadIdx.x, dst = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const int src = from[dst] - 1;
+    if (src < 0 || src >= S || src == dst) return;
+    if (tile == 0 && tid == 0) {
+        const unsigned a = active[src], c = cmd[S + src];
+        active[dst] = a;
+        cmd[S + dst] = c;
+    }
+    for (int i = 0; i < sp.n; ++i) {
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        const float4* ps = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
+                                                           (unsigned long long)src * sp.s[i].bytes);
+        float4* pd = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)dst * sp.s[i].bytes);
+        const long hi = n16 * (tile + 1) / ntile;
+        for (long j = n16 * tile / ntile + tid; j < hi; j += (long)SM_U * SS_NT) {
+            float4 v[SM_U];
+#pragma unroll
+            for (int u = 0; u < SM_U; ++u) v[u] = ps[min(j + (long)u * SS_NT, hi - 1)];
+#pragma unroll
+            for (int u = 0; u < SM_U; ++u)
+                if (j + (long)u * SS_NT < hi) pd[j + (long)u * SS_NT] = v[u];
+        }
     }
 }
 
@@ -456,6 +592,46 @@ extern "C" int lh_session_end(const lh_span_t* spans, int n_spans, const float* 
     if (!chunk_in || !out || !cmd || !active || !fault || S <= 0 || n_spans > SE_SP || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
     hipLaunchKernelGGL(k_session_end, dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, chunk_in, out, cmd, active, fault, S);
+    return check_launch();
+}
+
+namespace lh {
+static int sess_tiles(int n) { return n <= 16 ? 64 : (n >= 64 ? 16 : 1024 / n); }     // as lh_session_begin, per row launched
+}  // namespace lh
+
+extern "C" int lh_session_move(const lh_span_t* spans, int n_spans, const int* from, unsigned* cmd, unsigned* active, int n_rows,
+                               int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!from || !cmd || !active || S <= 0 || n_rows < 1 || n_rows > S || !sess_spans(spans, n_spans, sp)) return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_move, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, from, cmd,
+                       active, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_begin_rows(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk,
+                                     const unsigned* cmd, const unsigned* active, const int* slot_of, int n_rows, int S,
+                                     lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || !slot_of || S <= 0 || n_rows < 1 || n_rows > S ||
+        !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_begin_rows, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in,
+                       chunk, cmd, active, slot_of, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_end_rows(const lh_span_t* spans, int n_spans, const float* chunk_in, const float* out_rows, float* out,
+                                   unsigned* cmd, unsigned* active, unsigned* fault, const int* slot_of, const int* row_of,
+                                   int* from, int n_rows, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!chunk_in || !out_rows || !out || out_rows == out || !cmd || !active || !fault || !slot_of || !row_of || S <= 0 ||
+        n_rows < 1 || n_rows > S || n_spans > SE_SP || !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_end_rows, dim3(n_rows + 1), dim3(SE_NT), 0, (hipStream_t)stream, sp, chunk_in, out_rows, out,
+                       cmd, active, fault, slot_of, row_of, from, n_rows, S);
     return check_launch();
 }
 

@@ -347,11 +347,14 @@ class Net(_cabi.HipHost, nn.Module):
         """Chunked real-time front end (BASELINE configs[1]): see `Streamer`."""
         return Streamer(self, batch_size, device, use_graph)
 
-    def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0):
+    def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
+                              compact: bool = False, row_buckets=None):
         """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
         `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
-        enrollment embedder runs beside the chunk loop and the slot opens itself on the result."""
-        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks)
+        enrollment embedder runs beside the chunk loop and the slot opens itself on the result.
+        `compact`: open listeners are kept in the leading rows and a chunk is launched for the smallest of `row_buckets`
+        (ascending launch sizes ending in n_slots; default: the powers of two below n_slots, and n_slots) that holds them."""
+        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets)
 
     def _enroll_side(self, dev) -> _EnrollSide:
         return _EnrollSide(dev, self.enroll_low_priority)
@@ -1106,13 +1109,36 @@ class SessionStreamer:
     once.  `close(slot)` cancels a capture or a running embedding (a result that arrives later is dropped by its
     generation), `reset()` cancels all of them.  Call the embedder once on a clip of this length before the loop starts:
     its first call packs weights.
-    Not built: idle slots still cost their share of every launch (rows are not compacted); slots advance in lock-step."""
+    Compaction (`compact=True`; False, the default, builds exactly the object above): a chunk costs what its listeners cost.
+    Slots keep their numbers towards the caller — every method above, the rows of `step`'s input and output, the fault
+    words — while the open listeners live in the leading ROWS of the same state buffers, and `step` runs the chunk's kernels
+    for `last_rows` = the smallest of `row_buckets` that holds the `rows_in_use` rows (one alternating graph pair per
+    bucket, over the leading rows of the same buffers and workspace).  An opening takes the first free row.  When a
+    listener leaves — `close`, or a fault word `step` sees — the survivors in the rows at and above the new row count move
+    into the holes below it, highest row first: every move has src >= the new count > dst, so the moves of one step are
+    disjoint and run in one launch (`lh_session_move`, the chunk's first node: the row's slice of every state tensor, its
+    speaker gain, its `active` and pending device command word — bytes, the listener keeps their bits).  An opening of the
+    same step takes the uppermost of the holes, which saves that move.  `lh_session_begin_rows` / `lh_session_end_rows` gather
+    the row's input from, and scatter its output to, the slot; rows without a listener are idle on the device whatever they
+    still hold, and a slot without a row is written zeros in every chunk.  Moves, the row <-> slot maps and the commands travel
+    in the one asynchronous copy, only when something is pending.  A slot that is capturing or embedding owns no row.
+    Not built: slots advance in lock-step."""
     RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
     ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
 
-    def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0):
+    def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0, compact: bool = False,
+                 row_buckets=None):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
+        if row_buckets is not None and not compact:
+            raise ValueError("row_buckets are the launch sizes of a compacting streamer: compact=True")
+        if compact:
+            if row_buckets is None:
+                row_buckets = [1 << i for i in range(n_slots.bit_length()) if 1 << i < n_slots] + [n_slots]
+            row_buckets = tuple(int(b) for b in row_buckets)
+            if not row_buckets or row_buckets[0] < 1 or row_buckets[-1] != n_slots or \
+                    any(a >= b for a, b in zip(row_buckets, row_buckets[1:])):
+                raise ValueError(f"row_buckets must ascend from >= 1 to n_slots = {n_slots}, got {row_buckets}")
         if enroll_chunks < 0 or enroll_chunks == 1:
             raise ValueError("enroll_chunks must be 0 (no enrollment) or >= 2: the embedder needs 4 STFT frames at stride 64, "
                              "192 samples, and a chunk records 128")
@@ -1122,15 +1148,31 @@ class SessionStreamer:
         S, dev = n_slots, st.device
         self.chunk_in = torch.zeros_like(st.chunk)          # as the clients sent it; `st.chunk` is the gated copy
         self.out = st.out
-        self._words = torch.zeros(3, S, dtype=torch.int32, device=dev)       # cmd from the host | cmd from the device | active
+        self.compact, self.row_buckets = bool(compact), row_buckets
+        if compact:
+            # rows of words: move table | row -> slot | slot -> row | cmd from the host || cmd from the device | active.
+            # The first four are the host's (one copy), the last three the [2][S] cmd and the [S] active of the kernels
+            self.out = torch.zeros_like(st.out)             # by SLOT; `st.out` is by row
+            self._tables = torch.zeros(6, S, dtype=torch.int32, device=dev)
+            self._tables[1:3].fill_(-1)
+            self._words = self._tables[3:]
+            self._row_of, self._slot_of = [-1] * S, [-1] * S                 # as of the last `step`
+            self._n_rows = 0
+            self._last_rows = row_buckets[0]
+            # slot and generation of the listener in each row: one vector compare per `step` finds a fault word
+            self._slot_np, self._rgen_np = np.zeros(S, dtype=np.int64), np.full(S, -1, dtype=np.int64)
+        else:
+            self._words = torch.zeros(3, S, dtype=torch.int32, device=dev)   # cmd from the host | cmd from the device | active
         self._fault = net._host_words(S, dev)
         self._fault_np = self._fault.numpy()                # the same memory, read without a tensor op per slot
         span = lambda t: _Span(t.data_ptr(), t.numel() * t.element_size() // S)
         state = [t for x in st.sets for t in [x["conv_buf"], x["deconv_buf"], x["istft_buf"]] + x["h"] + x["c"]]
         state += [t for kv in st.rings for t in kv]
-        if len(state) > self.MAX_SPANS:
-            raise ValueError(f"{len(state)} state tensors, lh_session_begin takes {self.MAX_SPANS}")
+        if len(state) + compact > self.MAX_SPANS:
+            raise ValueError(f"{len(state) + compact} state tensors, lh_session_begin / lh_session_move take {self.MAX_SPANS}")
         self._spans = (_Span * len(state))(*[span(t) for t in state])
+        if compact:                                         # what a row owns: its state and its speaker gain
+            self._spans_move = (_Span * (len(state) + 1))(*[span(t) for t in state + [st.gain]])
         # what chunk k WRITES: the (h, c) of the other ping-pong set
         self._spans_end = [(_Span * (2 * net.n_blocks))(*[span(t) for t in st.sets[k ^ 1]["h"] + st.sets[k ^ 1]["c"]])
                            for k in (0, 1)]
@@ -1153,10 +1195,15 @@ class SessionStreamer:
         self.graphs = None
         if use_graph:
             with torch.no_grad():
-                self.graphs = Streamer._capture(self._body, dev)
+                if compact:                                 # one alternating pair per launch size
+                    self.graphs = {n: Streamer._capture(lambda k, n=n: self._body(k, n), dev) for n in row_buckets}
+                else:
+                    self.graphs = Streamer._capture(self._body, dev)
             self.reset()
 
-    def _body(self, k: int):
+    def _body(self, k: int, n_rows: int = 0):
+        if self.compact:
+            return self._body_rows(k, n_rows)
         st, net, S = self._st, self.net, self.S
         P = lambda t: t.data_ptr()
         with net._device_ctx(st.chunk):
@@ -1173,9 +1220,38 @@ class SessionStreamer:
             lib.call("lh_session_end", ctypes.addressof(self._spans_end[k]), len(self._spans_end[k]), P(self.chunk_in),
                      P(st.out), cmd, active, P(self._fault), S, stream)
 
+    def _body_rows(self, k: int, n: int):
+        """The chunk of a compacting streamer for its leading `n` rows: move -> begin -> (capture) -> chunk -> ring advance ->
+        end.  Every per-row tensor is row-major in the batch index, so the leading rows of the same buffers are a batch of n."""
+        st, net, S = self._st, self.net, self.S
+        P = lambda t: t.data_ptr()
+        with net._device_ctx(st.chunk):
+            lib, stream = net._lib(st.chunk), net._stream(self.device)
+            t = self._tables
+            frm, slot_of, row_of, cmd, active = P(t[0]), P(t[1]), P(t[2]), P(t[3]), P(t[5])
+            lib.call("lh_session_move", ctypes.addressof(self._spans_move), len(self._spans_move), frm, cmd, active, n, S, stream)
+            lib.call("lh_session_begin_rows", ctypes.addressof(self._spans), len(self._spans), P(self.chunk_in), P(st.chunk), cmd,
+                     active, slot_of, n, S, stream)
+            if self.enroll_chunks:                          # by slot: a capturing slot owns no row
+                lib.call("lh_session_capture", P(self.chunk_in), P(self._clips), P(self._ewords), P(self._ewords[1]),
+                         P(self._edone), self.enroll_chunks, S, stream)
+            net._stream_chunk(st.chunk[:n], st.gain, st.sets[k], st.sets[k ^ 1], st.rings, st.pos, st.out, st._pk, st._ws, None,
+                              keep_nonfinite=1)
+            lib.call("lh_ring_advance", P(st.pos), net.local_atten_len, stream)
+            lib.call("lh_session_end_rows", ctypes.addressof(self._spans_end[k]), len(self._spans_end[k]), P(self.chunk_in),
+                     P(st.out), P(self.out), cmd, active, P(self._fault), slot_of, row_of, frm, n, S, stream)
+
     def reset(self):
         """Every slot idle, all state zero (what a new SessionStreamer starts from).  Captures and embeddings are cancelled."""
         self._st.reset()
+        if self.compact:
+            self._tables.zero_()
+            self._tables[1:3].fill_(-1)
+            self.out.zero_()
+            self._row_of, self._slot_of = [-1] * self.S, [-1] * self.S
+            self._n_rows = 0
+            self._last_rows = self.row_buckets[0]
+            self._rgen_np.fill(-1)
         self._words.zero_()
         self._fault.zero_()
         self._gen = [0] * self.S
@@ -1232,11 +1308,62 @@ class SessionStreamer:
             raise ValueError(f"slot {slot} was not opened by enrollment")
         return self._enrolled[slot]
 
+    @property
+    def rows_in_use(self) -> int:
+        """Rows that held a listener in the last `step` (a lock-step streamer: every slot is a row)."""
+        return self._n_rows if self.compact else self.S
+
+    @property
+    def last_rows(self) -> int:
+        """The batch the last `step` launched its kernels for: the bucket of `rows_in_use`."""
+        return self._last_rows if self.compact else self.S
+
     def _set_gain(self, slot: int, embed: torch.Tensor):
         st = self._st
         st.embed[slot].copy_(embed.reshape(-1), non_blocking=True)
+        row = self._row_of[slot] if self.compact else slot
+        if row >= 0:                                        # else: `_plan` does it once the slot has a row
+            self._row_gain(slot, row)
+
+    def _row_gain(self, slot: int, row: int):
+        st = self._st
         with torch.no_grad():                               # this row only, eager, stream-ordered before the next replay
-            self.net._speaker_gain(st.embed[slot:slot + 1], st.gain_raw[slot:slot + 1], st.gain[slot:slot + 1])
+            self.net._speaker_gain(st.embed[slot:slot + 1], st.gain_raw[row:row + 1], st.gain[row:row + 1])
+
+    def _plan(self):
+        """The rows of the next chunk, from the rows of the last one: listeners that left give their rows up, survivors above
+        the new row count move into the holes below it, openings take the holes that are left — and the tables that tell the
+        device, in one asynchronous copy."""
+        S, f, gen, pend = self.S, self._fault_np, self._gen, self._pending
+        row_of, slot_of, n_old = self._row_of, self._slot_of, self._n_rows
+        for r in range(n_old):                              # closed by the host, or by the device and seen now
+            s = slot_of[r]
+            if not gen[s] or int(f[s]) == gen[s]:
+                slot_of[r], row_of[s] = -1, -1
+        opens = [s for s, w in pend.items() if w & self.OPEN and row_of[s] < 0]
+        keep = [r for r in range(n_old) if slot_of[r] >= 0]
+        n = len(keep) + len(opens)
+        holes = [r for r in range(n) if r >= n_old or slot_of[r] < 0]
+        movers = [r for r in reversed(keep) if r >= n]     # src >= n > dst: disjoint, one launch
+        src = self.net._host_words(4 * S, self.device)      # a FRESH pinned array per batch, as for the commands alone
+        words = src.numpy().reshape(4, S)
+        for dst, r in zip(holes, movers):
+            s = slot_of[r]
+            slot_of[dst], row_of[s], slot_of[r] = s, dst, -1
+            words[0, dst] = r + 1
+        for s, dst in zip(opens, holes[len(movers):]):
+            slot_of[dst], row_of[s] = s, dst
+            self._row_gain(s, dst)                          # a hole or a new row: never the source of a move
+        words[1], words[2] = slot_of, row_of
+        for s, w in pend.items():
+            if w & self.OPEN:                               # a row whose listener left needs no word: it has no slot
+                words[3, row_of[s]] = w
+        pend.clear()
+        self._tables[:4].copy_(src.view(4, S), non_blocking=True)
+        self._n_rows = n
+        self._slot_np[:n] = slot_of[:n]
+        self._rgen_np[:n] = [gen[s] for s in slot_of[:n]]
+        self._rgen_np[n:] = -1
 
     def _open(self, slot: int, embed: torch.Tensor):
         gen = self._new_gen()
@@ -1341,7 +1468,12 @@ class SessionStreamer:
         st._check_repacked()
         st._check_versions()
         self.poll()
-        if self._pending:
+        if self.compact:
+            n = self._n_rows
+            if self._pending or (n and (self._fault_np[self._slot_np[:n]] == self._rgen_np[:n]).any()):
+                self._plan()
+            self._last_rows = next(b for b in self.row_buckets if b >= self._n_rows)
+        elif self._pending:
             # a FRESH pinned array per batch of commands: the host allocator hands its memory out again only after the
             # copy below has run, so a host that runs ahead of the device cannot overwrite commands in flight
             src = self.net._host_words(self.S, self.device)
@@ -1359,9 +1491,11 @@ class SessionStreamer:
             self._ewords[0].copy_(src, non_blocking=True)
         self.chunk_in.copy_(chunks)
         with torch.no_grad():
-            if self.graphs is not None:
-                self.graphs[st.parity].replay()
+            if self.graphs is None:
+                self._body(st.parity, self.last_rows)
+            elif self.compact:
+                self.graphs[self._last_rows][st.parity].replay()
             else:
-                self._body(st.parity)
+                self.graphs[st.parity].replay()
         st.parity ^= 1
         return self.out

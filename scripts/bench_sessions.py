@@ -12,6 +12,10 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         against a streamer built without it, interleaved in one run; (b) the chunks that overlap a running embedder call, one
         and four slots embedding, side stream at default and at lowest priority; (c) steps from the capture's last chunk to
         the slot's appearance in `active`.  The loop waits for every chunk's end event, as a real-time consumer does.
+    python scripts/bench_sessions.py --compact [--slots 64] [--open 1,4,16,64] [--out profiles/xyz.txt]
+        what row compaction buys and costs, in DEVICE time per chunk as above: (a) S slots with k listeners open, the lock-step
+        streamer against the compacting one, blocks of the two interleaved in one run; `scatter` is the spread of the lock-step
+        blocks' p50; (b) a step that moves one row and a step that moves eight, against the steps around them.
 """
 import argparse
 import json
@@ -155,9 +159,72 @@ def enroll_bench(net, args):
             f.write(text + "\n")
 
 
+def compact_bench(net, args):
+    S, reps = args.slots, 4
+    d = synth.batch(list(range(S)), 80000)
+    mix = torch.nn.functional.pad(d["mixture"], (0, 64)).to(DEV)
+    emb = d["embedding_gt"][:, 0].to(DEV)
+    chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+    pair = {"lock-step": net.make_session_streamer(S, DEV), "compact": net.make_session_streamer(S, DEV, compact=True)}
+    lines = [f"row compaction, device time per chunk (HIP events around each replay), S = {S}, buckets "
+             f"{pair['compact'].row_buckets}, {args.steps} steps per figure in {reps} interleaved blocks after {args.warmup} warm-up"]
+    # ---- (a) occupancy: k listeners open in both, blocks interleaved
+    for k in [int(v) for v in args.open.split(",")]:
+        ms, p50s = {n: [] for n in pair}, {n: [] for n in pair}
+        for ss in pair.values():
+            ss.reset()
+            for s in range(k):
+                ss.open(s, emb[s])
+            dev_steps(ss, chunks, 0, args.warmup)
+        for rep in range(reps):
+            for n, ss in pair.items():
+                blk = [a.elapsed_time(b) for a, b in dev_steps(ss, chunks, 0, args.steps // reps)]
+                ms[n] += blk
+                p50s[n].append(pct(blk, 0.5))
+        torch.cuda.synchronize()
+        assert all(ss.faults() == [] and len(ss.active) == k for ss in pair.values())
+        rl, rc = stats(ms["lock-step"]), stats(ms["compact"])
+        scatter = max(p50s["lock-step"]) - min(p50s["lock-step"])
+        gain = rl["p50_ms"] - rc["p50_ms"]
+        lines.append(f"(a) {k:3d} of {S} open, launched for {pair['compact'].last_rows:3d} rows   lock-step: p50 {rl['p50_ms']:.4f} p99 "
+                     f"{rl['p99_ms']:.4f} ms   compact: p50 {rc['p50_ms']:.4f} p99 {rc['p99_ms']:.4f} ms   lock-step minus compact "
+                     f"{1e3 * gain:+.1f} us, scatter of the lock-step blocks {1e3 * scatter:.1f} us: "
+                     f"{'MORE' if gain > 3 * scatter else 'NOT more'} than three times the scatter")
+    # ---- (b) the move step: all open, then the lowest m slots close in one step, so m rows move in its launch
+    ss = pair["compact"]
+    for m in (1, 8):
+        if m >= S:
+            continue
+        quiet, moving = [], []
+        for rep in range(args.move_reps):
+            ss.reset()
+            for s in range(S):
+                ss.open(s, emb[s])
+            evs = dev_steps(ss, chunks, 0, 12)
+            quiet += [a.elapsed_time(b) for a, b in evs[4:]]
+            for s in range(m):
+                ss.close(s)
+            (a, b), = dev_steps(ss, chunks, 12, 1)
+            moving.append(a.elapsed_time(b))
+            assert ss.rows_in_use == S - m
+        rq, rm = stats(quiet), stats(moving)
+        lines.append(f"(b) a step that moves {m} row{'s' if m > 1 else ' '} ({S} -> {S - m} listeners, {rm['n']} times): p50 "
+                     f"{rm['p50_ms']:.4f} max {rm['max_ms']:.4f} ms   the steps before it: p50 {rq['p50_ms']:.4f} p99 "
+                     f"{rq['p99_ms']:.4f} ms   p50 cost {1e3 * (rm['p50_ms'] - rq['p50_ms']):+.1f} us")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--enroll", action="store_true")
+    ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--slots", type=int, default=64)
+    ap.add_argument("--open", default="1,4,16,64")
+    ap.add_argument("--move-reps", type=int, default=20)
     ap.add_argument("--enroll-chunks", type=int, default=625)
     ap.add_argument("--batches", default="1,64")
     ap.add_argument("--steps", type=int, default=625)
@@ -171,6 +238,8 @@ def main():
     net = net.to(DEV)
     if args.enroll:
         return enroll_bench(net, args)
+    if args.compact:
+        return compact_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)

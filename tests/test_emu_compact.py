@@ -1,0 +1,293 @@
+"""CPU: `SessionStreamer(compact=True)` (net.py) and its three kernels (`lh_session_move`, `lh_session_begin_rows`,
+`lh_session_end_rows`, lh_stream.hip) over the emulated library, eager.  Open listeners live in the leading rows; a listener
+that leaves makes the survivors above move down, and a chunk is launched for the bucket of the rows in use.  A move is a copy
+of bytes, so the claims about it are `torch.equal` on integers; a session is compared with the oracle's forward over its OWN
+samples from the zero state within the emulator tolerance of tests/test_emu_kernels.py.  Small on purpose (S = 3, under ten
+chunks per case): the emulator runs a chunk row in ~0.5 s."""
+import ctypes
+
+import pytest
+import torch
+
+from lookoncetohear_amd import _cabi, synth
+from lookoncetohear_amd.net import _Span
+from tests.hipemu.hosts import EmuNet
+from oracle import tfgridnet_oracle as O
+
+TOL = 5e-5          # tests/test_emu_kernels.py
+HOP, NFFT = 128, 192
+RESET, OPEN, CLOSE, SHIFT = 1, 2, 4, 8
+ARG = 1
+
+
+class EmuSessionNet(EmuNet):
+    def _host_words(self, n, device):               # the pinned words of the GPU host: plain host memory here
+        return torch.zeros(n, dtype=torch.int32)
+
+
+@pytest.fixture(scope="module")
+def emu_net(oracle_cfg_sd):
+    from tests.hipemu.build_emu import build_emu
+    cfg, sd = oracle_cfg_sd
+    net = EmuSessionNet(**O.TSH_PARAMS).eval()
+    net.load_state_dict(sd, strict=True)
+    net.emu_lib = _cabi.Lib(build_emu())
+    return net
+
+
+@pytest.fixture(scope="module")
+def clips():
+    """Three 10-chunk binaural mixtures with their speaker embeddings."""
+    d = synth.batch([20, 21, 22], HOP * 10 + NFFT - HOP)
+    return d["mixture"], d["embedding_gt"][:, 0]
+
+
+def chunk_of(mix_row, j):
+    return mix_row[:, j * HOP:j * HOP + NFFT]
+
+
+def fresh_stream(oracle_cfg_sd, mix_row, emb_row, n):
+    cfg, sd = oracle_cfg_sd
+    y, _ = O.predict(cfg, sd, mix_row[None, :, :HOP * n + NFFT - HOP], emb_row[None], None, pad=False)
+    return y[0]
+
+
+def run(ss, S, n, feed, events=None, after=None):
+    """n steps; feed(i) -> {slot: chunk [2, 192]} (rows not named are NaN), events {i: fn} run before step i, after(i) after
+    it.  Returns [S, 2, 128 n]."""
+    outs = []
+    for i in range(n):
+        if events and i in events:
+            events[i]()
+        x = torch.full((S, 2, NFFT), float("nan"))
+        for slot, c in feed(i).items():
+            x[slot] = c
+        outs.append(ss.step(x).clone())
+        if after:
+            after(i)
+    return torch.cat(outs, -1)
+
+
+# ---- the three entry points on hand-made buffers -------------------------------------------------------------------------
+def patterns(*shape):
+    """Random 32-bit patterns, NaN and inf patterns among them: a move must copy bytes, not numbers."""
+    t = torch.randint(-2 ** 31, 2 ** 31 - 1, shape, dtype=torch.int64).to(torch.int32)
+    flat = t.view(-1)
+    special = torch.tensor([0x7fc00000, 0x7f800000, -0x800000, 0x7f800001, -1, 0x7fffffff], dtype=torch.int64).to(torch.int32)
+    idx = torch.randperm(flat.numel())[:max(6, flat.numel() // 50)]
+    flat[idx] = special[torch.arange(idx.numel()) % special.numel()]
+    return t
+
+
+class Rows:
+    """S rows of four span tensors (one longer than a tile's single pass: 64 tiles x 256 threads x 4 loads), and the words."""
+
+    def __init__(self, lib, S, big=70000 * 4):
+        torch.manual_seed(7)
+        self.lib, self.S = lib, S
+        self.t = [patterns(S, 7, 4), patterns(S * 3, 4), patterns(S, 1000, 4), patterns(S, big)]
+        self.bytes = [112, 48, 16000, big * 4]
+        self.spans = (_Span * 4)(*[_Span(t.data_ptr(), b) for t, b in zip(self.t, self.bytes)])
+        self.tables = torch.zeros(6, S, dtype=torch.int32)          # from | slot_of | row_of | cmd host | cmd device | active
+        self.tables[3:] = patterns(3, S)
+
+    def row(self, i, r):
+        return self.t[i].view(self.S, -1)[r]
+
+    def move(self, n_rows, raw=False):
+        t = self.tables
+        args = (ctypes.addressof(self.spans), 4, t[0].data_ptr(), t[3].data_ptr(), t[5].data_ptr(), n_rows, self.S, None)
+        if raw:                                                 # the status, not an exception
+            return self.lib.raw("lh_session_move")(*args)
+        self.lib.call("lh_session_move", *args)
+
+
+def test_move_is_byte_exact(emu_net):
+    S = 5
+    k = Rows(emu_net.emu_lib, S)
+    before, words = [t.clone() for t in k.t], k.tables.clone()
+    # an empty table, and entries that name no row or the row itself: nothing moves
+    k.move(S)
+    k.tables[0] = torch.tensor([0, S + 1, 3, -4, 0], dtype=torch.int32)
+    k.move(S)
+    assert all(torch.equal(a, b) for a, b in zip(k.t, before)) and torch.equal(k.tables[1:], words[1:])
+    # two disjoint pairs in one launch over the three leading rows: 3 -> 0, 4 -> 1; row 2 has no entry
+    k.tables[0] = torch.tensor([4, 5, 0, 0, 0], dtype=torch.int32)
+    k.move(3)
+    for i in range(4):
+        old = before[i].view(S, -1)
+        assert torch.equal(k.row(i, 0), old[3]) and torch.equal(k.row(i, 1), old[4]), i       # integers: NaN == NaN here
+        assert torch.equal(k.t[i].view(S, -1)[2:], old[2:]), i                                  # sources and bystanders
+    cmd_dev, active = k.tables[4].tolist(), k.tables[5].tolist()
+    w = words.tolist()
+    assert cmd_dev == [w[4][3], w[4][4]] + w[4][2:] and active == [w[5][3], w[5][4]] + w[5][2:]
+    assert k.tables[3].tolist() == w[3]                         # the host's command words are the host's to address
+    assert k.tables[0].tolist() == [4, 5, 0, 0, 0]              # read-only here: lh_session_end_rows takes the entries out
+    # an entry beyond the rows launched is not looked at
+    again = [t.clone() for t in k.t]
+    k.tables[0] = torch.tensor([0, 0, 0, 1, 0], dtype=torch.int32)
+    k.move(3)
+    assert all(torch.equal(a, b) for a, b in zip(k.t, again))
+    assert k.move(0, raw=True) == ARG and k.move(S + 1, raw=True) == ARG and k.move(S, raw=True) == 0
+
+
+def test_row_kernels_gather_scatter_and_report_by_slot(emu_net):
+    """Rows 0, 1 hold slots 2 and 0 of S = 4; row 2 of the 3 launched has no slot; slots 1, 3 have no row."""
+    lib, S, n = emu_net.emu_lib, 4, 3
+    a = torch.ones(S, 7, 4)
+    spans = (_Span * 1)(_Span(a.data_ptr(), 112))
+    x, gated = torch.randn(S, 2, NFFT), torch.full((S, 2, NFFT), 9.0)
+    rows_out, out = torch.randn(S, 2, HOP), torch.full((S, 2, HOP), 9.0)
+    t = torch.zeros(6, S, dtype=torch.int32)
+    t[1] = torch.tensor([2, 0, -1, -1], dtype=torch.int32)
+    t[2] = torch.tensor([1, -1, 0, -1], dtype=torch.int32)
+    fault = torch.zeros(S, dtype=torch.int32)
+    P, sp = (lambda v: v.data_ptr()), ctypes.addressof(spans)
+
+    def chunk():
+        lib.call("lh_session_begin_rows", sp, 1, P(x), P(gated), P(t[3]), P(t[5]), P(t[1]), n, S, None)
+        lib.call("lh_session_end_rows", sp, 1, P(x), P(rows_out), P(out), P(t[3]), P(t[5]), P(fault), P(t[1]), P(t[2]), P(t[0]),
+                 n, S, None)
+    # open both rows (generations 5, 6); row 2 carries a stale `active` word and an OPEN nobody may act on: it has no slot
+    t[3, 0], t[3, 1], t[3, 2] = RESET | OPEN | (5 << SHIFT), RESET | OPEN | (6 << SHIFT), OPEN | (9 << SHIFT)
+    t[5, 2] = 7
+    t[0, 1] = 3                                                  # a served move entry
+    x[1] = float("nan")                                          # slots without a row: their input is never looked at
+    lib.call("lh_session_begin_rows", sp, 1, P(x), P(gated), P(t[3]), P(t[5]), P(t[1]), n, S, None)
+    assert torch.equal(gated[0], x[2]) and torch.equal(gated[1], x[0]) and not gated[2].any() and gated[3].eq(9).all()
+    assert not a[0].any() and not a[1].any() and a[2].eq(1).all() and a[3].eq(1).all()
+    a.fill_(1.0)
+    lib.call("lh_session_end_rows", sp, 1, P(x), P(rows_out), P(out), P(t[3]), P(t[5]), P(fault), P(t[1]), P(t[2]), P(t[0]),
+             n, S, None)
+    assert torch.equal(out[2], rows_out[0]) and torch.equal(out[0], rows_out[1]) and not out[1].any() and not out[3].any()
+    assert t[5].tolist() == [5, 6, 0, 0] and not t[3:5].any() and not t[0].any() and not fault.any()
+    # non-finite input of slot 0 (row 1): reported under the SLOT, the row zeroed and idle; slot 2 keeps its row's samples
+    x[0, 1, 5] = float("inf")
+    out.fill_(9.0)
+    chunk()
+    assert fault.tolist() == [6, 0, 0, 0] and t[5].tolist() == [5, 0, 0, 0]
+    assert not a[1].any() and a[0].eq(1).all() and not gated[1].any()
+    assert torch.equal(out[2], rows_out[0]) and not out[0].any() and not out[1].any() and not out[3].any()
+    # overflow in row 0's output: fault[2], RESET posted on the ROW
+    rows_out[0, 0, 3] = float("nan")
+    chunk()
+    assert fault.tolist() == [6, 0, 5, 0] and t[4].tolist() == [RESET, 0, 0, 0] and not out.any()
+    raw_b, raw_e = lib.raw("lh_session_begin_rows"), lib.raw("lh_session_end_rows")
+    V = lambda v: ctypes.c_void_p(v.data_ptr())
+    q = ctypes.c_void_p(sp)
+    assert raw_b(q, 1, V(x), V(gated), V(t[3]), V(t[5]), V(t[1]), n, S, None) == 0
+    assert raw_b(q, 1, V(x), V(gated), V(t[3]), V(t[5]), None, n, S, None) == ARG
+    assert raw_b(q, 1, V(x), V(gated), V(t[3]), V(t[5]), V(t[1]), S + 1, S, None) == ARG
+    assert raw_b(q, 1, V(x), V(gated), V(t[3]), V(t[5]), V(t[1]), 0, S, None) == ARG
+    assert raw_e(q, 1, V(x), V(rows_out), V(out), V(t[3]), V(t[5]), V(fault), V(t[1]), V(t[2]), None, n, S, None) == 0
+    assert raw_e(q, 1, V(x), V(out), V(out), V(t[3]), V(t[5]), V(fault), V(t[1]), V(t[2]), None, n, S, None) == ARG
+    assert raw_e(q, 1, V(x), V(rows_out), V(out), V(t[3]), V(t[5]), V(fault), V(t[1]), None, None, n, S, None) == ARG
+    assert raw_e(q, 1, V(x), V(rows_out), V(out), V(t[3]), V(t[5]), V(fault), V(t[1]), V(t[2]), None, S + 1, S, None) == ARG
+
+
+# ---- the host's bookkeeping over the emulated device ---------------------------------------------------------------------
+def test_schedule_with_opens_closes_and_a_fault(emu_net, clips, oracle_cfg_sd):
+    """Slots 2, 0 open at chunk 0 (rows 0, 1), slot 1 at chunk 2 (row 2); slot 2 closes at chunk 4: slot 1 moves 2 -> 0.
+    Slot 1's chunk 6 holds a NaN: the fault is reported under slot 1 although its row is 0, and the step after it slot 0 moves
+    1 -> 0."""
+    mix, emb = clips
+    S, n = 3, 9
+    ss = emu_net.make_session_streamer(S, "cpu", use_graph=False, compact=True)
+    assert ss.row_buckets == (1, 2, 3) and ss.rows_in_use == 0
+    ss.open(2, emb[2]), ss.open(0, emb[0])
+    start = {2: 0, 0: 0, 1: 2}
+
+    def feed(i):
+        f = {0: chunk_of(mix[0], i)}
+        if i < 4:
+            f[2] = chunk_of(mix[2], i)
+        if i >= 2:
+            f[1] = chunk_of(mix[1], i - 2).clone()
+            if i == 6:
+                f[1][0, 100] = float("nan")
+        return f
+    seen = []
+    y = run(ss, S, n, feed, {2: lambda: ss.open(1, emb[1]), 4: lambda: ss.close(2)},
+            after=lambda i: seen.append((list(ss._slot_of), ss.rows_in_use, ss.last_rows, ss.faults(), ss.active)))
+    two, three = ([2, 0, -1], 2, 2, [], [0, 2]), ([2, 0, 1], 3, 3, [], [0, 1, 2])
+    moved = ([1, 0, -1], 2, 2, [], [0, 1])
+    assert seen[:2] == [two] * 2 and seen[2:4] == [three] * 2 and seen[4:6] == [moved] * 2
+    assert seen[6] == ([1, 0, -1], 2, 2, [1], [0])              # the device's word is there when the chunk is done ...
+    assert seen[7] == seen[8] == ([0, -1, -1], 1, 1, [1], [0])  # ... and the next step gives the row up
+    assert ss._row_of == [0, -1, -1]
+    z = lambda k: torch.zeros(2, k * HOP)
+    assert float((y[0] - fresh_stream(oracle_cfg_sd, mix[0], emb[0], n)).abs().max()) < TOL          # rows 1, 1, 0
+    assert float((y[2, :, :4 * HOP] - fresh_stream(oracle_cfg_sd, mix[2], emb[2], 4)).abs().max()) < TOL
+    e1 = float((y[1, :, 2 * HOP:6 * HOP] - fresh_stream(oracle_cfg_sd, mix[1], emb[1], 4)).abs().max())
+    print("slot 1, opened in row 2 and moved to row 0 after two chunks: max|emu - oracle fresh stream| =", e1)
+    assert e1 < TOL
+    assert torch.equal(y[1, :, :2 * HOP], z(2)) and torch.equal(y[1, :, 6 * HOP:], z(3)) and torch.equal(y[2, :, 4 * HOP:], z(5))
+    # the slot opens again as a fresh stream in the next free row
+    ss.open(1, emb[2])
+    y2 = run(ss, S, 2, lambda i: {0: chunk_of(mix[0], 0), 1: chunk_of(mix[2], i)})
+    assert ss._slot_of == [0, 1, -1] and ss.faults() == [] and ss.active == [0, 1]
+    assert float((y2[1] - fresh_stream(oracle_cfg_sd, mix[2], emb[2], 2)).abs().max()) < TOL
+
+
+@pytest.fixture(scope="module")
+def three_then_two(emu_net, clips):
+    """The clean run of the in-flight cases: three listeners, slot 0 closes at chunk 2.  [3, 2, 128 * 5]"""
+    mix, emb = clips
+    ss = emu_net.make_session_streamer(3, "cpu", use_graph=False, compact=True)
+    for s in range(3):
+        ss.open(s, emb[s])
+    return run(ss, 3, 5, lambda i: {s: chunk_of(mix[s], i) for s in range(3) if s or i < 2}, {2: lambda: ss.close(0)})
+
+
+@pytest.mark.parametrize("late", [False, True], ids=["same_chunk", "word_not_seen_yet"])
+def test_host_moves_a_row_the_device_is_closing(emu_net, clips, three_then_two, late):
+    """Slot 0 closes at chunk 2, so the host moves slot 2's listener from row 2 to row 0 — while the device closes that very
+    listener for a NaN: in the chunk of the move (`same_chunk`), or in the chunk before it with the fault word reaching the
+    host only after the move was posted (`word_not_seen_yet`: the word is held back here, the emulator has no latency)."""
+    mix, emb = clips
+    S, n, bad_at = 3, 5, 1 if late else 2
+    ss = emu_net.make_session_streamer(S, "cpu", use_graph=False, compact=True)
+    for s in range(S):
+        ss.open(s, emb[s])
+    gen2 = ss._gen[2]
+
+    def feed(i):
+        f = {s: chunk_of(mix[s], i).clone() for s in range(S) if s or i < 2}
+        if i == bad_at:
+            f[2][1, 3] = float("nan")
+        return f
+    held = {}
+
+    def hold_back():                                            # after chunk 1: the word exists, the host has not read it
+        held["w"] = int(ss._fault_np[2])
+        ss._fault_np[2] = 0
+
+    def after(i):
+        if late and i == 1:
+            hold_back()
+        if late and i == 2:
+            ss._fault_np[2] = held["w"]                         # arrives: the same word, one step late
+        held[i] = (list(ss._slot_of), ss.rows_in_use, ss.faults())
+    y = run(ss, S, n, feed, {2: lambda: ss.close(0)}, after)
+    if late:
+        assert held["w"] == gen2
+    assert held[2] == ([2, 1, -1], 2, [2])                      # moved as planned, reported under its slot
+    assert held[3] == held[4] == ([1, -1, -1], 1, [2])          # given up one step later; slot 1 moves 1 -> 0
+    assert torch.equal(y[1], three_then_two[1])                 # the neighbour keeps its bits through both moves
+    assert torch.equal(y[2, :, :bad_at * HOP], three_then_two[2, :, :bad_at * HOP])
+    assert torch.equal(y[2, :, bad_at * HOP:], torch.zeros(2, (n - bad_at) * HOP))
+    assert torch.equal(y[0], three_then_two[0]) and torch.isfinite(y).all()
+    assert ss._tables[5].tolist()[0] == ss._gen[1] and ss.active == [1]
+
+
+def test_compact_arguments(emu_net):
+    mk = emu_net.make_session_streamer
+    with pytest.raises(ValueError):
+        mk(4, "cpu", use_graph=False, row_buckets=(2, 4))       # buckets without compaction
+    for bad in ((), (2, 3), (4, 2), (2, 2, 4), (0, 4)):
+        with pytest.raises(ValueError):
+            mk(4, "cpu", use_graph=False, compact=True, row_buckets=bad)
+    assert mk(5, "cpu", use_graph=False, compact=True).row_buckets == (1, 2, 4, 5)
+    assert mk(4, "cpu", use_graph=False, compact=True, row_buckets=[4]).row_buckets == (4,)
+    ss = mk(2, "cpu", use_graph=False)
+    assert not ss.compact and ss.rows_in_use == 2 and ss.last_rows == 2
