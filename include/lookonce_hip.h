@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (17); bumped on any signature change. */
+/* ABI version of this header (19); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -218,6 +218,17 @@ int lh_qkv_proj_ln(const float* y, const void* w_pk, const float* bias, const fl
                    const float* lnv_b, void* q, void* kx, void* vx, const int* ring_pos, int B, int T,
                    lh_stream_t stream);
 
+/* lh_qkv_proj_ln for one-frame chunks (T = 1) whose rows each own a ring position (ABI 19, paced sessions below):
+ *   write_pos  [B] device words: row b writes its K and V rows into ring slot write_pos[b] (mod 50) of its persistent
+ *              rings; a NEGATIVE entry writes no K / V row (a held or idle row of a paced host).  The Q row is written
+ *              either way.  The zero pad rows behind the 50 ring rows are written by neither form.
+ * Row b's Q / K / V bits are those of lh_qkv_proj_ln with *ring_pos = write_pos[b]: a separate instantiation of the same
+ * kernel body. */
+int lh_qkv_proj_ln_rows(const float* y, const void* w_pk, const float* bias, const float* slopes, const float* lnq_w,
+                        const float* lnq_b, const float* lnk_w, const float* lnk_b, const float* lnv_w,
+                        const float* lnv_b, void* q, void* kx, void* vx, const int* write_pos, int B,
+                        lh_stream_t stream);
+
 /* A.3.5  local windowed attention over exactly 50 slots (frames t-49..t incl. history rows, no mask) with
  * the head merge fused into the store.  Replaces tfgridnet_causal.py:564-581 without materialising the
  * 50x unfolded K/V (`_causal_unfold_chunk`, :429-454).
@@ -236,6 +247,9 @@ int lh_ring_unpack(const void* kx, const void* vx, float* k_buf, float* v_buf, i
  * stream order — one node of the captured per-chunk graph (the reference has no counterpart: it shifts K_buf / V_buf by
  * one row per chunk, tfgridnet_causal.py:553-562).  modulo in [1, 2^30]. */
 int lh_ring_advance(int* ring_pos, int modulo, lh_stream_t stream);
+/* Per-row form (ABI 19): pos[r] = (write_pos[r] + 1) mod modulo where write_pos[r] >= 0, untouched otherwise, r < n_rows.
+ * The only writer of a paced host's ring positions apart from a row move.  LH_ERR_ARG: null, pos == write_pos, n_rows < 1. */
+int lh_ring_advance_rows(int* pos, const int* write_pos, int modulo, int n_rows, lh_stream_t stream);
 
 /* A.3.6  attn_concat_proj: Linear(64->64)+PReLU, joint LayerNorm over (f,c), residual; optional speaker gain.
  * Replaces tfgridnet_causal.py:583-588 and, when gain != NULL, the `batch = batch * embed` applied to the
@@ -466,7 +480,7 @@ int lh_metric_sums(const float* outputs, const float* target, const float* mixtu
 int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B, int n_samples,
                      int sr, int frame, double rms_threshold, lh_stream_t stream);
 
-/* ---- streaming sessions (ABI 16 - 18) ----------------------------------------------------------------------------------------
+/* ---- streaming sessions (ABI 16 - 19) ----------------------------------------------------------------------------------------
  * A batched streaming host serves S listener SLOTS in lock-step (one 8 ms chunk of every slot per step; slot = batch row of
  * every streaming entry point above).  These two launches bracket the chunk's launch sequence — first and last node of a
  * captured per-chunk graph — and let slots open, close and fail one at a time, on the device and without a host wait (the
@@ -568,6 +582,51 @@ int lh_session_end_rows(const lh_span_t* spans, int n_spans, const float* chunk_
 enum { LH_ENROLL_ARM = 1, LH_ENROLL_CANCEL = 2, LH_ENROLL_GEN_SHIFT = 8, LH_ENROLL_FAULT = 0x80000000u };
 int lh_session_capture(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone, int n_chunks,
                        int S, lh_stream_t stream);
+
+/* Paced sessions (ABI 19): a listener whose chunk is late is HELD for the step — the other slots are not stalled and the
+ * held one is, after the step, bit for bit what it was before.  Every row owns its K / V ring position, so a listener's
+ * samples depend on their own chunks only: not on when the slot was opened, not on who else was held.  The entry points
+ * above with three more device arrays; their lock-step forms are untouched and a host uses one family or the other.
+ *   hold       [S] words by SLOT (the row forms look them up through slot_of), non-zero = held in this step.  Posted by the
+ *              host like cmd, only when the mask changes.
+ *   pos        [S] the ROW's ring position in [0, 50), zero at start.  Written by lh_ring_advance_rows, copied by
+ *              lh_session_move_paced with the row, by nothing else.
+ *   write_pos  [S] per row, written by the begin entry points for lh_qkv_proj_ln_rows and lh_ring_advance_rows: -1 for a row
+ *              that is held or not live, 0 for a row serving a RESET (OPEN comes with RESET), pos[r] otherwise.
+ *   carry      2 n_pairs spans (host array, validated and passed like `spans`): carry[2 i] a state tensor the chunk READ,
+ *              carry[2 i + 1] the tensor of the other ping-pong set it WROTE in its place — the conv, deconv and iSTFT tails
+ *              and (h, c) of every block.  2 n_pairs <= LH_SESSION_MAX_SPANS, equal sizes, distinct bases.
+ * Call order of one chunk:  (lh_session_move_paced ->) lh_session_begin[_rows]_paced -> (lh_session_capture_paced) ->
+ * the chunk's launches with lh_qkv_proj_ln_rows(write_pos) in place of lh_qkv_proj_ln -> lh_ring_advance_rows ->
+ * lh_session_end[_rows]_paced.
+ * A held row:  its input row is not looked at (it may be NaN) and zeros go to the separator;  write_pos = -1, so no K / V row
+ * is written and pos stays;  the end entry point passes no verdict on what the kernels made of the zeros, writes zeros to the
+ * row's output and copies the row's slice of every carry[2 i] over carry[2 i + 1] with 16-byte loads and stores — bytes, not
+ * numbers.  A held row costs what a live row costs: pacing buys correctness under jitter, not time.
+ * Commands are served whether or not the row is held.  CLOSE: as above.  RESET (with OPEN): begin zeroes the state, so the
+ * zeros are carried; the row is active; and end posts RESET again in cmd[1][r] for as long as the row is held, so the chunk
+ * that takes the listener's first samples zeroes once more and starts the ring at slot 0.
+ * A capturing slot that is held serves ARM / CANCEL, records nothing and is not judged: the clip is the samples of the
+ * chunks the slot was present for.
+ * LH_ERR_ARG: as for the lock-step forms, and a null hold / pos / write_pos, pos == write_pos, n_pairs < 1 or too many, a pair
+ * of unequal sizes or one tensor twice.  None of them allocates or synchronises. */
+int lh_session_begin_paced(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk, const unsigned* cmd,
+                           const unsigned* active, const unsigned* hold, const int* pos, int* write_pos, int S,
+                           lh_stream_t stream);
+int lh_session_end_paced(const lh_span_t* spans, int n_spans, const lh_span_t* carry, int n_pairs, const float* chunk_in,
+                         float* out, unsigned* cmd, unsigned* active, unsigned* fault, const unsigned* hold, int S,
+                         lh_stream_t stream);
+int lh_session_move_paced(const lh_span_t* spans, int n_spans, const int* from, unsigned* cmd, unsigned* active, int* pos,
+                          int n_rows, int S, lh_stream_t stream);
+int lh_session_begin_rows_paced(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk, const unsigned* cmd,
+                                const unsigned* active, const int* slot_of, const unsigned* hold, const int* pos,
+                                int* write_pos, int n_rows, int S, lh_stream_t stream);
+int lh_session_end_rows_paced(const lh_span_t* spans, int n_spans, const lh_span_t* carry, int n_pairs, const float* chunk_in,
+                              const float* out_rows, float* out, unsigned* cmd, unsigned* active, unsigned* fault,
+                              const unsigned* hold, const int* slot_of, const int* row_of, int* from, int n_rows, int S,
+                              lh_stream_t stream);
+int lh_session_capture_paced(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone,
+                             const unsigned* hold, int n_chunks, int S, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -42,6 +42,15 @@ SIGNATURES = {
     "lh_session_move": [_P, _I, _P, _P, _P, _I, _I, _P],
     "lh_session_begin_rows": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],
     "lh_session_end_rows": [_P, _I] + [_P] * 9 + [_I, _I, _P],
+    # paced sessions (ABI 19): per-row K / V ring positions and held rows, SessionStreamer(pace=True)
+    "lh_qkv_proj_ln_rows": [_P] * 14 + [_I, _P],
+    "lh_ring_advance_rows": [_P, _P, _I, _I, _P],
+    "lh_session_begin_paced": [_P, _I] + [_P] * 7 + [_I, _P],
+    "lh_session_end_paced": [_P, _I, _P, _I] + [_P] * 6 + [_I, _P],
+    "lh_session_move_paced": [_P, _I, _P, _P, _P, _P, _I, _I, _P],
+    "lh_session_begin_rows_paced": [_P, _I] + [_P] * 8 + [_I, _I, _P],
+    "lh_session_end_rows_paced": [_P, _I, _P, _I] + [_P] * 10 + [_I, _I, _P],
+    "lh_session_capture_paced": [_P] * 6 + [_I, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)

@@ -422,6 +422,25 @@ extern "C" int lh_ring_advance(int* ring_pos, int modulo, lh_stream_t stream) {
     return lh::check_launch();
 }
 
+namespace lh {
+// one thread per row: the only writer of a paced session host's per-row ring positions (lh_stream.hip, "paced sessions")
+__global__ void k_ring_advance_rows(int* pos, const int* __restrict__ write_pos, int modulo, int n_rows) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const int w = write_pos[r];
+    if (w < 0) return;                             // the row consumed no chunk
+    const int p = (int)((unsigned)w % (unsigned)modulo) + 1;
+    pos[r] = p >= modulo ? 0 : p;
+}
+}  // namespace lh
+
+extern "C" int lh_ring_advance_rows(int* pos, const int* write_pos, int modulo, int n_rows, lh_stream_t stream) {
+    if (!pos || !write_pos || pos == write_pos || modulo < 1 || modulo > (1 << 30) || n_rows < 1) return LH_ERR_ARG;
+    hipLaunchKernelGGL(lh::k_ring_advance_rows, dim3((n_rows + 63) / 64), dim3(64), 0, (hipStream_t)stream, pos, write_pos,
+                       modulo, n_rows);
+    return lh::check_launch();
+}
+
 extern "C" int lh_ring_unpack(const void* kx, const void* vx, float* k_buf, float* v_buf, int B, int T,
                               lh_stream_t stream) {
     using namespace lh;

@@ -241,6 +241,11 @@ __device__ __forceinline__ void qkv_products(const _Float16* ahi, const _Float16
     });
 }
 
+// ROWS (ABI 19: the one-frame chunks of a paced session host, lh_qkv_proj_ln_rows) is a template flag, not a run-time branch
+// in the persistent loop: the lock-step instantiation sits at 249 of 256 VGPRs and stays, instruction for instruction, the
+// code it was.  With ROWS (T = Tc = 1, tw0 = 0) `ring_pos` is write_pos[B]: frame b writes its K / V rows into ring slot
+// write_pos[b], a negative entry writes neither (a held or idle row: its Q row is still written, from the zero-gated input).
+template <bool ROWS>
 __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict__ y, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slopes,
                                                      const float* __restrict__ lnq_w, const float* __restrict__ lnq_b,
@@ -295,7 +300,7 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
     // K / V row of frame t: HIST + t behind the history rows — or, for a one-frame chunk on a persistent ring
     // (ring_pos != NULL, T = 1), slot (*ring_pos mod 50): the 50 rows are then exactly the attention window, in
     // rotated order, which softmax and P.V do not care about
-    const int krow0 = ring_pos ? (int)((unsigned)*ring_pos % (unsigned)WIN) : HIST;   // unsigned: never before the ring
+    const int krow0 = ROWS ? 0 : ring_pos ? (int)((unsigned)*ring_pos % (unsigned)WIN) : HIST;   // unsigned: never before the ring
     for (int fr = blockIdx.x; fr < nframes; fr += gridDim.x) {      // grid-stride over frames (b*T + t)
         const int b = fr / Tc, t = tw0 + fr % Tc;
         QKV_STAMP(0);
@@ -325,9 +330,12 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
         float* yk = yf + Y_K0 + hd * YQS;
         float* yv = yf + Y_V0 + hd * DV;
         const float* zero8 = yf + DQKP - 8;          // features 600..607 of Q head 0: always zero (16-byte aligned)
+        // ROWS: T = 1, fr = b; the row's own slot, wave-uniform
+        const int wp = ROWS ? ring_pos[fr] : 0;
+        const int krow = ROWS ? (int)((unsigned)wp % (unsigned)WIN) : krow0;
         _Float16* qrow = q + (bh * T + t) * LDQKH;
-        _Float16* krow = kx + (bh * tkp + krow0 + t) * LDQKH;
-        _Float16* vrow = vx + (bh * tkp + krow0 + t) * LDVH;
+        _Float16* krow_p = kx + (bh * tkp + krow + t) * LDQKH;
+        _Float16* vrow = vx + (bh * tkp + krow + t) * LDVH;
         // `fr >> 30` is always 0 but ties the lane index to the loop variable: without it LICM hoists every slot address
         // of the three rows (and V's affine) out of the persistent frame loop and the kernel spills
         const int ln = lane + (fr >> 30);
@@ -340,10 +348,10 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
             const float vq = lq.center(mq, ln), vk = lk.center(mk, ln);
             const float rq = rsqrtf(wave_sum(vq) * (1.0f / DQK) + LN_EPS), rk = rsqrtf(wave_sum(vk) * (1.0f / DQK) + LN_EPS);
             lq.store<0>(rq, qrow, ln);
-            lk.store<0>(rk, krow, ln);
+            if (!ROWS || wp >= 0) lk.store<0>(rk, krow_p, ln);
         }
         QKV_STAMP(4);
-        {
+        if (!ROWS || wp >= 0) {
             HeadLN<DV, DV / 4> lv;
             lv.load_affine(lnv_w, lnv_b, ln);
             const float sv1 = lv.read(yv, zero8, ln);
@@ -540,7 +548,7 @@ extern "C" int lh_qkv_proj_ln_win(const float* y, const void* w_pk, const float*
         !vx || B <= 0 || T <= 0 || (ring_pos && T != 1) || t0 < 0 || Tc <= 0 || t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL(k_qkv_proj_ln, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
+    hipLaunchKernelGGL(k_qkv_proj_ln<false>, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
                        (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
                        (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
     return check_launch();
@@ -552,6 +560,20 @@ extern "C" int lh_qkv_proj_ln(const float* y, const void* w_pk, const float* bia
                               int B, int T, lh_stream_t stream) {
     return lh_qkv_proj_ln_win(y, w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, q, kx, vx, ring_pos, B, T, 0, T,
                               stream);
+}
+
+extern "C" int lh_qkv_proj_ln_rows(const float* y, const void* w_pk, const float* bias, const float* slopes,
+                                   const float* lnq_w, const float* lnq_b, const float* lnk_w, const float* lnk_b,
+                                   const float* lnv_w, const float* lnv_b, void* q, void* kx, void* vx, const int* write_pos,
+                                   int B, lh_stream_t stream) {
+    using namespace lh;
+    if (!y || !w_pk || !bias || !slopes || !lnq_w || !lnq_b || !lnk_w || !lnk_b || !lnv_w || !lnv_b || !q || !kx || !vx ||
+        !write_pos || B <= 0)
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_qkv_proj_ln<true>, dim3(B < 512 ? B : 512), dim3(256), 0, (hipStream_t)stream, y,
+                       (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
+                       (_Float16*)kx, (_Float16*)vx, 1, B, write_pos, 1, 0);
+    return check_launch();
 }
 
 extern "C" int lh_proj_ln_res_win(const float* merged, const void* w_pk, const float* bias, const float* slope,

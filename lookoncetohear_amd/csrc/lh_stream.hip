@@ -528,6 +528,212 @@ __global__ void __launch_bounds__(SC_NT) k_session_capture(const float* __restri
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Paced sessions (ABI 19): a listener whose chunk is late is HELD for the step instead of stalling the others.  hold[S] is
+// one more input word per SLOT (the row forms look it up through slot_of), posted by the host like the commands; pos[S] is
+// the row's own K / V ring position and write_pos[S] what the chunk's kernels get of it.  Who writes what, as above: every
+// decision is a function of unmodified inputs (cmd, active, hold, the input row).  Tile 0 of k_session_begin_paced writes
+// write_pos[row]: -1 for a held or non-live row (lh_qkv_proj_ln_rows then writes no K / V row), 0 for a row that serves a
+// RESET, pos[row] otherwise; lh_ring_advance_rows is the only writer of pos (k_session_move_paced copies it with the row);
+// k_session_end_paced stays the only writer of the words.  A held row's kernels still run, on the zero-gated input: the end
+// kernel throws their output away and copies the row's slice of every tensor of the ping-pong set the chunk READ over the set
+// it WROTE (bytes; the rings and pos were never touched), so after the step the row is, bit for bit, what it was before.
+// A held row is never judged: neither its input row nor what the kernels made of the zeros.  Its commands are served: CLOSE
+// as ever; a RESET is served by begin (the carried state is then the zeros) and posted again by end for as long as the row
+// is held, so that the chunk that takes the listener's first samples still finds it and starts the ring at 0.
+// One kernel each for the slot forms (slot_of == NULL: row r is slot r) and the row forms.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ SessRow sess_row_or_slot(const int* __restrict__ slot_of, int r, int S) {
+    return slot_of ? sess_row(slot_of, r, S) : SessRow{r, true};
+}
+__device__ __forceinline__ SessDecision sess_decide_paced(const SessLoads& l, bool held) {
+    SessDecision d = sess_decide(l);
+    if (held) d.bad_in = false, d.live = d.gen != 0;      // open and not consuming: live to the words, zeros to the separator
+    return d;
+}
+
+// grid (tiles, rows launched), block 256
+__global__ void __launch_bounds__(SS_NT) k_session_begin_paced(SessSpans sp, const float* __restrict__ chunk_in,
+                                                               float* __restrict__ chunk, const unsigned* __restrict__ cmd,
+                                                               const unsigned* __restrict__ active,
+                                                               const int* __restrict__ slot_of,
+                                                               const unsigned* __restrict__ hold, const int* __restrict__ pos,
+                                                               int* __restrict__ write_pos, int S) {
+    const int tid = threadIdx.x, r = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const SessRow w = sess_row_or_slot(slot_of, r, S);
+    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, tid & 63);
+    const unsigned h = hold[w.slot];
+    const int p = pos[r];
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[(long)w.slot * SS_IN4 + min(tid, SS_IN4 - 1)];
+    if (!w.owned) l.host = LH_SESSION_CLOSE;
+    const bool held = w.owned && h != 0u;
+    const SessDecision d = sess_decide_paced(l, held);
+    const bool takes = d.live && !held;            // the row consumes this chunk
+    if (tile == 0) {
+        if (tid < SS_IN4) reinterpret_cast<float4*>(chunk)[(long)r * SS_IN4 + tid] = takes ? mine : z;
+        if (tid == 0) write_pos[r] = !takes ? -1 : (d.cmd & LH_SESSION_RESET) ? 0 : p;
+    }
+    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
+    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the row's slice of every state tensor
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        float4* q = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)r * sp.s[i].bytes);
+        const long hi = n16 * (tile + 1) / ntile;
+        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) q[j] = z;
+    }
+}
+
+// grid rows launched (+ 1 in the row form: k_session_end_rows' last workgroup), block 1024.  sp: the (h, c) just written, as in
+// k_session_end; cp: the carry table, cp.s[2 i] the tensor the chunk read, cp.s[2 i + 1] the one it wrote in its place.
+__global__ void __launch_bounds__(SE_NT) k_session_end_paced(SessSpans sp, SessSpans cp, const float* __restrict__ chunk_in,
+                                                             const float* out_rows, float* out, unsigned* cmd,
+                                                             unsigned* active, unsigned* fault,
+                                                             const unsigned* __restrict__ hold,
+                                                             const int* __restrict__ slot_of, const int* __restrict__ row_of,
+                                                             int* from, int n_rows, int S) {
+    __shared__ int wbad[SE_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, r = blockIdx.x;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r >= n_rows) {                             // row form only: slots without a row among those launched
+        for (int q = tid >> 6; q < S; q += SE_NT / 64) {
+            const int qr = row_of[q];
+            if (qr < 0 || qr >= n_rows) reinterpret_cast<float4*>(out)[(long)q * SS_OUT4 + lane] = z;
+        }
+        return;
+    }
+    const SessRow w = sess_row_or_slot(slot_of, r, S);
+    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, lane);
+    const unsigned h = hold[w.slot];
+    const float4 ov = reinterpret_cast<const float4*>(out_rows)[(long)r * SS_OUT4 + (tid & (SS_OUT4 - 1))];
+    float4 v[SE_SP][SE_U];                         // branch-free, all requested before any is looked at (k_session_end)
+#pragma unroll
+    for (int i = 0; i < SE_SP; ++i) {
+        const lh_span_t sq = sp.s[i < sp.n ? i : 0];
+        const int last = (int)min((long)(sq.bytes >> 4), (long)SE_U * SE_NT) - 1;
+        const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)r * sq.bytes);
+#pragma unroll
+        for (int u = 0; u < SE_U; ++u) v[i][u] = q[min(tid + u * SE_NT, last)];
+    }
+    bool bad = nonfinite4(ov);
+#pragma unroll
+    for (int i = 0; i < SE_SP; ++i)
+#pragma unroll
+        for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
+    for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
+                                                          (unsigned long long)r * sp.s[i].bytes);
+        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(q[j]);
+    }
+    if (!w.owned) l.host = LH_SESSION_CLOSE;
+    const bool held = w.owned && h != 0u;          // uniform over the workgroup
+    if (held) {
+        // carry: what the chunk's kernels wrote from the zeros is overwritten with what the row had.  A thread's SM_U loads
+        // are requested together; thread t only ever touches elements t + k SE_NT, the ones it scanned above
+        for (int i = 0; i + 1 < cp.n; i += 2) {
+            const long n16 = (long)(cp.s[i].bytes >> 4);
+            const unsigned long long off = (unsigned long long)r * cp.s[i].bytes;
+            const float4* ps = reinterpret_cast<const float4*>(static_cast<const char*>(cp.s[i].base) + off);
+            float4* pd = reinterpret_cast<float4*>(static_cast<char*>(cp.s[i + 1].base) + off);
+            for (long j = tid; j < n16; j += (long)SM_U * SE_NT) {
+                float4 c[SM_U];
+#pragma unroll
+                for (int u = 0; u < SM_U; ++u) c[u] = ps[min(j + (long)u * SE_NT, n16 - 1)];
+#pragma unroll
+                for (int u = 0; u < SM_U; ++u)
+                    if (j + (long)u * SE_NT < n16) pd[j + (long)u * SE_NT] = c[u];
+            }
+        }
+    }
+    const SessDecision d = sess_decide_paced(l, held);
+    bad = wave_any(bad);
+    if (lane == 0) wbad[tid >> 6] = bad ? 1 : 0;
+    __syncthreads();                               // also: every wave has read the words thread 0 is about to write
+    int any = 0;
+#pragma unroll
+    for (int q = 0; q < SE_NT / 64; ++q) any |= wbad[q];
+    const bool overflow = d.live && !held && any != 0;      // a held row's scan has no verdict
+    const bool on = d.live && !overflow;
+    const bool sounds = on && !held;
+    if (w.owned && tid < SS_OUT4 && (!sounds || out_rows != out))
+        reinterpret_cast<float4*>(out)[(long)w.slot * SS_OUT4 + tid] = sounds ? ov : z;
+    if (tid == 0) {
+        active[r] = on ? d.gen : 0u;
+        if (w.owned) {
+            if (d.bad_in || overflow) __hip_atomic_store(&fault[w.slot], d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[w.slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        cmd[r] = 0u;
+        // held through its RESET: the row's first consumed chunk must still see it (ring position 0)
+        cmd[S + r] = (overflow || (held && on && (d.cmd & LH_SESSION_RESET))) ? (unsigned)LH_SESSION_RESET : 0u;
+        if (from) from[r] = 0;
+    }
+}
+
+// k_session_move, and the row's ring position with it
+__global__ void __launch_bounds__(SS_NT) k_session_move_paced(SessSpans sp, const int* __restrict__ from, unsigned* cmd,
+                                                              unsigned* active, int* pos, int S) {
+    const int tid = threadIdx.x, dst = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const int src = from[dst] - 1;
+    if (src < 0 || src >= S || src == dst) return;
+    if (tile == 0 && tid == 0) {
+        const unsigned a = active[src], c = cmd[S + src];
+        const int p = pos[src];
+        active[dst] = a;
+        cmd[S + dst] = c;
+        pos[dst] = p;
+    }
+    for (int i = 0; i < sp.n; ++i) {
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        const float4* ps = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
+                                                           (unsigned long long)src * sp.s[i].bytes);
+        float4* pd = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)dst * sp.s[i].bytes);
+        const long hi = n16 * (tile + 1) / ntile;
+        for (long j = n16 * tile / ntile + tid; j < hi; j += (long)SM_U * SS_NT) {
+            float4 v[SM_U];
+#pragma unroll
+            for (int u = 0; u < SM_U; ++u) v[u] = ps[min(j + (long)u * SS_NT, hi - 1)];
+#pragma unroll
+            for (int u = 0; u < SM_U; ++u)
+                if (j + (long)u * SS_NT < hi) pd[j + (long)u * SS_NT] = v[u];
+        }
+    }
+}
+
+// k_session_capture for a paced host: a held slot's commands are served, its row is neither recorded nor judged
+__global__ void __launch_bounds__(SC_NT) k_session_capture_paced(const float* __restrict__ chunk_in, float* __restrict__ enroll,
+                                                                 unsigned* ecmd, unsigned* estate, unsigned* edone,
+                                                                 const unsigned* __restrict__ hold, int n_chunks, int S) {
+    const int s = blockIdx.x, lane = threadIdx.x, ch = lane >> 5, q = lane & 31;
+    const unsigned cmd = ecmd[s], held = hold[s];
+    unsigned gen = estate[s], k = estate[S + s];
+    const float4 v = reinterpret_cast<const float4*>(chunk_in + ((long)s * NMIC + ch) * NFFT)[q];
+    if (cmd & LH_ENROLL_CANCEL) gen = 0u;
+    if (cmd & LH_ENROLL_ARM) {
+        gen = (cmd >> LH_ENROLL_GEN_SHIFT) & 0x7fffffu;
+        if (gen == 0u) gen = 1u;
+        k = 0u;
+    }
+    if (cmd == 0u && (gen == 0u || held != 0u)) return;      // wave-uniform: nothing posted, nothing to record
+    unsigned done = 0u;
+    if (gen != 0u && held == 0u) {
+        if (wave_any(nonfinite4(v))) {
+            done = gen | LH_ENROLL_FAULT;
+        } else {
+            k = min(k, (unsigned)n_chunks - 1u);
+            reinterpret_cast<float4*>(enroll + ((long)s * NMIC + ch) * HOP * n_chunks + (long)HOP * k)[q] = v;
+            if (++k == (unsigned)n_chunks) done = gen;
+        }
+    }
+    if (done != 0u || gen == 0u) gen = 0u, k = 0u;
+    if (lane == 0) {
+        if (cmd != 0u) ecmd[s] = 0u;
+        estate[s] = gen;
+        estate[S + s] = k;
+        if (done != 0u) __hip_atomic_store(&edone[s], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -642,5 +848,92 @@ extern "C" int lh_session_capture(const float* chunk_in, float* enroll, unsigned
     if (((unsigned long long)(size_t)enroll & 15) || ((unsigned long long)(size_t)chunk_in & 15)) return LH_ERR_ARG;
     hipLaunchKernelGGL(k_session_capture, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate, edone,
                        n_chunks, S);
+    return check_launch();
+}
+
+// ---- paced sessions (ABI 19) ------------------------------------------------------------------------------------------------
+namespace lh {
+// the carry table of lh_session_end_paced: n_pairs x (read, written), equal sizes
+static bool sess_pairs(const lh_span_t* carry, int n_pairs, SessSpans& cp) {
+    if (n_pairs < 1 || 2 * n_pairs > LH_SESSION_MAX_SPANS || !sess_spans(carry, 2 * n_pairs, cp)) return false;
+    for (int i = 0; i < n_pairs; ++i)
+        if (carry[2 * i].bytes != carry[2 * i + 1].bytes || carry[2 * i].base == carry[2 * i + 1].base) return false;
+    return true;
+}
+}  // namespace lh
+
+extern "C" int lh_session_begin_paced(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk,
+                                      const unsigned* cmd, const unsigned* active, const unsigned* hold, const int* pos,
+                                      int* write_pos, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || !hold || !pos || !write_pos || pos == write_pos ||
+        S <= 0 || !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_begin_paced, dim3(sess_tiles(S), S), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in, chunk,
+                       cmd, active, (const int*)nullptr, hold, pos, write_pos, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_begin_rows_paced(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk,
+                                           const unsigned* cmd, const unsigned* active, const int* slot_of,
+                                           const unsigned* hold, const int* pos, int* write_pos, int n_rows, int S,
+                                           lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || !slot_of || !hold || !pos || !write_pos ||
+        pos == write_pos || S <= 0 || n_rows < 1 || n_rows > S || !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_begin_paced, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp,
+                       chunk_in, chunk, cmd, active, slot_of, hold, pos, write_pos, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_end_paced(const lh_span_t* spans, int n_spans, const lh_span_t* carry, int n_pairs,
+                                    const float* chunk_in, float* out, unsigned* cmd, unsigned* active, unsigned* fault,
+                                    const unsigned* hold, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp, cp;
+    if (!chunk_in || !out || !cmd || !active || !fault || !hold || S <= 0 || n_spans > SE_SP || !sess_spans(spans, n_spans, sp) ||
+        !sess_pairs(carry, n_pairs, cp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_end_paced, dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, cp, chunk_in, (const float*)out,
+                       out, cmd, active, fault, hold, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, S, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_end_rows_paced(const lh_span_t* spans, int n_spans, const lh_span_t* carry, int n_pairs,
+                                         const float* chunk_in, const float* out_rows, float* out, unsigned* cmd,
+                                         unsigned* active, unsigned* fault, const unsigned* hold, const int* slot_of,
+                                         const int* row_of, int* from, int n_rows, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp, cp;
+    if (!chunk_in || !out_rows || !out || out_rows == out || !cmd || !active || !fault || !hold || !slot_of || !row_of ||
+        S <= 0 || n_rows < 1 || n_rows > S || n_spans > SE_SP || !sess_spans(spans, n_spans, sp) ||
+        !sess_pairs(carry, n_pairs, cp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_end_paced, dim3(n_rows + 1), dim3(SE_NT), 0, (hipStream_t)stream, sp, cp, chunk_in, out_rows,
+                       out, cmd, active, fault, hold, slot_of, row_of, from, n_rows, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_move_paced(const lh_span_t* spans, int n_spans, const int* from, unsigned* cmd, unsigned* active,
+                                     int* pos, int n_rows, int S, lh_stream_t stream) {
+    using namespace lh;
+    SessSpans sp;
+    if (!from || !cmd || !active || !pos || S <= 0 || n_rows < 1 || n_rows > S || !sess_spans(spans, n_spans, sp))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_move_paced, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, from,
+                       cmd, active, pos, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_capture_paced(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone,
+                                        const unsigned* hold, int n_chunks, int S, lh_stream_t stream) {
+    using namespace lh;
+    if (!chunk_in || !enroll || !ecmd || !estate || !edone || !hold || S <= 0 || n_chunks < 1) return LH_ERR_ARG;
+    if (((unsigned long long)(size_t)enroll & 15) || ((unsigned long long)(size_t)chunk_in & 15)) return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_capture_paced, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate,
+                       edone, hold, n_chunks, S);
     return check_launch();
 }

@@ -348,13 +348,14 @@ class Net(_cabi.HipHost, nn.Module):
         return Streamer(self, batch_size, device, use_graph)
 
     def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
-                              compact: bool = False, row_buckets=None):
+                              compact: bool = False, row_buckets=None, pace: bool = False):
         """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
         `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
         enrollment embedder runs beside the chunk loop and the slot opens itself on the result.
         `compact`: open listeners are kept in the leading rows and a chunk is launched for the smallest of `row_buckets`
-        (ascending launch sizes ending in n_slots; default: the powers of two below n_slots, and n_slots) that holds them."""
-        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets)
+        (ascending launch sizes ending in n_slots; default: the powers of two below n_slots, and n_slots) that holds them.
+        `pace`: `step(chunks, present=...)` holds the listeners whose chunk is late; every row owns its K / V ring position."""
+        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets, pace)
 
     def _enroll_side(self, dev) -> _EnrollSide:
         return _EnrollSide(dev, self.enroll_low_priority)
@@ -885,13 +886,15 @@ class Net(_cabi.HipHost, nn.Module):
                      P(gain_raw), P(gain), embed.shape[0], st)
 
     def _stream_chunk(self, x, gain, sin: dict, sout: dict, rings, pos, y, pk: dict, ws: dict, flag=None,
-                      keep_nonfinite: int = 0):
+                      keep_nonfinite: int = 0, write_pos=None):
         """One chunk of ONE frame for `Streamer`: the launches of `_separate` with every state tensor read from `sin` and
         written to `sout` (preallocated), the K / V history in per-block persistent rings, the speaker gain given.
         `pk` / `ws`: the packed weights and the T=1 workspace, OWNED by the caller — a captured graph holds raw pointers
         into them, so they must not be the entries `_weights` / `_workspace` may replace or evict later.
         `keep_nonfinite`: lh_deconv_istft's switch — 0 for `Streamer` (silence, not NaN, reaches a listener), 1 for
-        `SessionStreamer`, whose own last kernel looks at the samples and silences the slot."""
+        `SessionStreamer`, whose own last kernel looks at the samples and silences the slot.
+        `write_pos` [B] (a paced `SessionStreamer`): every row's own ring slot, negative = the row writes no K / V row
+        (`lh_qkv_proj_ln_rows`); `pos` is then not looked at."""
         lib = self._lib(x)
         dev = x.device
         hop, nfft = self.stft_chunk_size, self.nfft
@@ -913,9 +916,14 @@ class Net(_cabi.HipHost, nn.Module):
                      2 * H_, st)
             lib.call("lh_inter_block", P(xb), P(bp["inter_w8"]), P(bp["inter_b16"]), P(bp["inter_lin_wu"]),
                      P(bp["inter_lin_b"]), P(sin["h"][i]), P(sin["c"][i]), P(sout["h"][i]), P(sout["c"][i]), P(xc), Bn, T, st)
-            lib.call("lh_qkv_proj_ln", P(xc), P(bp["qkv_w"]), P(bp["qkv_b"]), P(bp["qkv_slopes"]), P(bp["lnq_w"]),
-                     P(bp["lnq_b"]), P(bp["lnk_w"]), P(bp["lnk_b"]), P(bp["lnv_w"]), P(bp["lnv_b"]), P(ws["q"]),
-                     P(kx), P(vx), P(pos), Bn, T, st)
+            if write_pos is None:
+                lib.call("lh_qkv_proj_ln", P(xc), P(bp["qkv_w"]), P(bp["qkv_b"]), P(bp["qkv_slopes"]), P(bp["lnq_w"]),
+                         P(bp["lnq_b"]), P(bp["lnk_w"]), P(bp["lnk_b"]), P(bp["lnv_w"]), P(bp["lnv_b"]), P(ws["q"]),
+                         P(kx), P(vx), P(pos), Bn, T, st)
+            else:
+                lib.call("lh_qkv_proj_ln_rows", P(xc), P(bp["qkv_w"]), P(bp["qkv_b"]), P(bp["qkv_slopes"]), P(bp["lnq_w"]),
+                         P(bp["lnq_b"]), P(bp["lnk_w"]), P(bp["lnk_b"]), P(bp["lnv_w"]), P(bp["lnv_b"]), P(ws["q"]),
+                         P(kx), P(vx), P(write_pos), Bn, st)
             lib.call("lh_local_attn", P(ws["q"]), P(kx), P(vx), P(xb), Bn, T, st)
             g = gain if (i == 0 and self.n_blocks > 1) else None
             lib.call("lh_proj_ln_res", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
@@ -1122,12 +1130,25 @@ class SessionStreamer:
     the row's input from, and scatter its output to, the slot; rows without a listener are idle on the device whatever they
     still hold, and a slot without a row is written zeros in every chunk.  Moves, the row <-> slot maps and the commands travel
     in the one asynchronous copy, only when something is pending.  A slot that is capturing or embedding owns no row.
-    Not built: slots advance in lock-step."""
+    Pacing (`pace=True`; False, the default, builds exactly the object above, launch for launch): listeners do not arrive in
+    lock-step.  `step(chunks, present)` HOLDS every slot whose `present[s]` is false: its input row is ignored (it may be NaN
+    and is never judged for a fault), its output row is exact zeros, and every bit of its carried state — tails, (h, c), K / V
+    rings and ring position — is after the step what it was before.  A listener's output stream is the concatenation of the
+    output rows of the steps they were present for.  Every ROW owns its ring position: the chunk that serves an OPEN sets it
+    to 0 and only a chunk the row consumed advances it (`lh_qkv_proj_ln_rows`, `lh_ring_advance_rows`), so in a paced streamer
+    a listener's bits depend on their own chunks only — not on when they were opened, not on who else was held.  Commands are
+    served whether or not the slot is held: a slot opened and held in the same step is reset and active, and its first chunk
+    is the first one it is present for; a capturing slot that is held records nothing, its clip is the samples of the chunks
+    it was present for.  With `compact=True` the position word moves with the row, and the hold words stay addressed by slot.
+    The hold words travel like the commands, a fresh pinned array copied asynchronously, and only in a step whose mask differs
+    from the one on the device: a steady all-present loop copies nothing.  A held row costs what a live row costs — its
+    kernels run on a zero-gated input and `lh_session_end_paced` puts the row's state back, about 0.2 MB of copies — so
+    pacing buys correctness under jitter, not time; a compacting streamer does not skip held rows."""
     RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
     ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
 
     def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0, compact: bool = False,
-                 row_buckets=None):
+                 row_buckets=None, pace: bool = False):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
         if row_buckets is not None and not compact:
@@ -1176,6 +1197,17 @@ class SessionStreamer:
         # what chunk k WRITES: the (h, c) of the other ping-pong set
         self._spans_end = [(_Span * (2 * net.n_blocks))(*[span(t) for t in st.sets[k ^ 1]["h"] + st.sets[k ^ 1]["c"]])
                            for k in (0, 1)]
+        self.pace = bool(pace)
+        if pace:
+            self._ring = torch.zeros(2, S, dtype=torch.int32, device=dev)    # per row: ring position | the chunk's write slot
+            self._hold = torch.zeros(S, dtype=torch.int32, device=dev)       # per slot, as of the last copy: `_held`
+            self._none_held = self._held = (False,) * S
+            # what a held row gets back: (read, written) of every tail and (h, c), for chunk k
+            carry = lambda x: [x["conv_buf"], x["deconv_buf"], x["istft_buf"]] + x["h"] + x["c"]
+            pairs = [[t for rw in zip(carry(st.sets[k]), carry(st.sets[k ^ 1])) for t in rw] for k in (0, 1)]
+            if len(pairs[0]) > self.MAX_SPANS:
+                raise ValueError(f"{len(pairs[0]) // 2} state pairs, lh_session_end_paced takes {self.MAX_SPANS // 2}")
+            self._spans_carry = [(_Span * len(p))(*[span(t) for t in p]) for p in pairs]
         self._gen = [0] * S                                 # generation of the slot's current opening, 0 = idle
         self._next_gen = 1
         self._pending = {}                                  # slot -> command word for the next step
@@ -1202,6 +1234,8 @@ class SessionStreamer:
             self.reset()
 
     def _body(self, k: int, n_rows: int = 0):
+        if self.pace:
+            return self._body_paced(k, n_rows)
         if self.compact:
             return self._body_rows(k, n_rows)
         st, net, S = self._st, self.net, self.S
@@ -1241,9 +1275,45 @@ class SessionStreamer:
             lib.call("lh_session_end_rows", ctypes.addressof(self._spans_end[k]), len(self._spans_end[k]), P(self.chunk_in),
                      P(st.out), P(self.out), cmd, active, P(self._fault), slot_of, row_of, frm, n, S, stream)
 
+    def _body_paced(self, k: int, n: int):
+        """The chunk of a paced streamer, lock-step rows (n = 0: every slot is a row) or the leading `n` rows of a compacting
+        one: (move ->) begin -> (capture) -> chunk with per-row ring slots -> per-row ring advance -> end."""
+        st, net, S = self._st, self.net, self.S
+        P, A = (lambda t: t.data_ptr()), ctypes.addressof
+        with net._device_ctx(st.chunk):
+            lib, stream = net._lib(st.chunk), net._stream(self.device)
+            hold, pos, wpos = P(self._hold), P(self._ring[0]), P(self._ring[1])
+            end, carry = self._spans_end[k], self._spans_carry[k]
+            if self.compact:
+                t = self._tables
+                frm, slot_of, row_of, cmd, active = P(t[0]), P(t[1]), P(t[2]), P(t[3]), P(t[5])
+                lib.call("lh_session_move_paced", A(self._spans_move), len(self._spans_move), frm, cmd, active, pos, n, S, stream)
+                lib.call("lh_session_begin_rows_paced", A(self._spans), len(self._spans), P(self.chunk_in), P(st.chunk), cmd,
+                         active, slot_of, hold, pos, wpos, n, S, stream)
+            else:
+                n, cmd, active = S, P(self._words), P(self._words[2])
+                lib.call("lh_session_begin_paced", A(self._spans), len(self._spans), P(self.chunk_in), P(st.chunk), cmd, active,
+                         hold, pos, wpos, S, stream)
+            if self.enroll_chunks:                          # by slot, like the hold words
+                lib.call("lh_session_capture_paced", P(self.chunk_in), P(self._clips), P(self._ewords), P(self._ewords[1]),
+                         P(self._edone), hold, self.enroll_chunks, S, stream)
+            net._stream_chunk(st.chunk[:n], st.gain, st.sets[k], st.sets[k ^ 1], st.rings, st.pos, st.out, st._pk, st._ws, None,
+                              keep_nonfinite=1, write_pos=self._ring[1])
+            lib.call("lh_ring_advance_rows", pos, wpos, net.local_atten_len, n, stream)
+            if self.compact:
+                lib.call("lh_session_end_rows_paced", A(end), len(end), A(carry), len(carry) // 2, P(self.chunk_in), P(st.out),
+                         P(self.out), cmd, active, P(self._fault), hold, slot_of, row_of, frm, n, S, stream)
+            else:
+                lib.call("lh_session_end_paced", A(end), len(end), A(carry), len(carry) // 2, P(self.chunk_in), P(st.out), cmd,
+                         active, P(self._fault), hold, S, stream)
+
     def reset(self):
         """Every slot idle, all state zero (what a new SessionStreamer starts from).  Captures and embeddings are cancelled."""
         self._st.reset()
+        if self.pace:
+            self._ring.zero_()
+            self._hold.zero_()
+            self._held = self._none_held
         if self.compact:
             self._tables.zero_()
             self._tables[1:3].fill_(-1)
@@ -1461,13 +1531,28 @@ class SessionStreamer:
                     self._enrolled[s] = out[i]
                     self._open(s, out[i])
 
-    def step(self, chunks: torch.Tensor) -> torch.Tensor:
+    def step(self, chunks: torch.Tensor, present=None) -> torch.Tensor:
         """chunks [S, 2, 192] (rows of idle slots are ignored) -> [S, 2, 128] (rows of idle slots are zeros); a view the next
-        `step` overwrites.  Never raises for a slot's fault: see `faults()`."""
+        `step` overwrites.  Never raises for a slot's fault: see `faults()`.
+        `present` (a paced streamer only): a length-S sequence or CPU bool tensor, false = the slot is held for this step —
+        its row of `chunks` is ignored, its output row is zeros, its state stays.  None: everyone is present."""
         st = self._st
+        if present is not None and not self.pace:
+            raise ValueError("`present` needs a paced streamer: make_session_streamer(..., pace=True)")
         st._check_repacked()
         st._check_versions()
         self.poll()
+        if self.pace:
+            held = self._none_held
+            if present is not None:
+                held = tuple(not p for p in (present.tolist() if isinstance(present, torch.Tensor) else present))
+                if len(held) != self.S:
+                    raise ValueError(f"`present` has {len(held)} entries for {self.S} slots")
+            if held != self._held:                          # a steady loop copies nothing; a FRESH pinned array, as below
+                src = self.net._host_words(self.S, self.device)
+                src.numpy()[:] = held
+                self._hold.copy_(src, non_blocking=True)
+                self._held = held
         if self.compact:
             n = self._n_rows
             if self._pending or (n and (self._fault_np[self._slot_np[:n]] == self._rgen_np[:n]).any()):

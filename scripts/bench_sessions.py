@@ -16,6 +16,12 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         what row compaction buys and costs, in DEVICE time per chunk as above: (a) S slots with k listeners open, the lock-step
         streamer against the compacting one, blocks of the two interleaved in one run; `scatter` is the spread of the lock-step
         blocks' p50; (b) a step that moves one row and a step that moves eight, against the steps around them.
+    python scripts/bench_sessions.py --pace [--batches 1,64] [--out profiles/xyz.txt]
+        what pacing costs, in DEVICE time per chunk as above, the lock-step streamer and the paced one interleaved in one run:
+        (a) every slot open and present, without a mask; (b) the largest batch with every second slot held; (c) the same with a
+        mask that changes in every step, which is the path that copies the hold words.
+    python scripts/bench_sessions.py --pace --trace idle|held --batches 64   # the short loop for rocprofv3, as above:
+        idle = everyone present; held = every second slot held
 """
 import argparse
 import json
@@ -74,6 +80,19 @@ def dev_steps(ss, chunks, i0, n, before=None, until=None):
         if until is not None and until():
             break
     return evs
+
+
+def dev_steps_present(ss, chunks, n, present_of):
+    """`dev_steps` of a paced streamer with the mask `present_of(i)` (None: no mask) -> ms per step."""
+    ms = []
+    for i in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ss.step(chunks[i % len(chunks)], present_of(i))
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
 
 
 def stats(ms):
@@ -218,9 +237,60 @@ def compact_bench(net, args):
             f.write(text + "\n")
 
 
+def pace_bench(net, args):
+    reps = 4
+    batches = [int(b) for b in args.batches.split(",")]
+    lines = [f"pacing cost, device time per chunk (HIP events around each replay), {args.steps} steps per figure in {reps} "
+             f"interleaved blocks after {args.warmup} warm-up; the yardstick is the lock-step SessionStreamer of the same run"]
+    for B in batches:
+        d = synth.batch(list(range(B)), 80000)
+        mix = torch.nn.functional.pad(d["mixture"], (0, 64)).to(DEV)
+        emb = d["embedding_gt"][:, 0].to(DEV)
+        chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+        lock, paced = net.make_session_streamer(B, DEV), net.make_session_streamer(B, DEV, pace=True)
+        for ss in (lock, paced):
+            for s in range(B):
+                ss.open(s, emb[s])
+        odd = [s % 2 == 0 for s in range(B)]
+        if args.trace:                           # a short loop for rocprofv3 --kernel-trace --stats
+            dev_steps_present(paced, chunks, 20, lambda i: None)         # everyone consumes a chunk first: no RESET is pending
+            dev_steps_present(paced, chunks, 200, (lambda i: odd) if args.trace == "held" else (lambda i: None))
+            continue
+        dev_steps(lock, chunks, 0, args.warmup)
+        dev_steps_present(paced, chunks, args.warmup, lambda i: None)
+        flip = [odd, [not p for p in odd]]
+        cases = [("(a) all present, no mask", lambda i: None)]
+        if B == max(batches) and B > 1:
+            cases += [("(b) every second slot held", lambda i: odd), ("(c) mask changes every step", lambda i: flip[i & 1])]
+        for name, present_of in cases:
+            ms, p50s = {"lock-step": [], "paced": []}, []
+            for rep in range(reps):
+                blk = [a.elapsed_time(b) for a, b in dev_steps(lock, chunks, 0, args.steps // reps)]
+                ms["lock-step"] += blk
+                p50s.append(pct(blk, 0.5))
+                ms["paced"] += dev_steps_present(paced, chunks, args.steps // reps, present_of)
+            torch.cuda.synchronize()
+            assert lock.faults() == [] and paced.faults() == [] and len(paced.active) == B
+            rl, rp = stats(ms["lock-step"]), stats(ms["paced"])
+            cost = rp["p50_ms"] - rl["p50_ms"]
+            lines.append(f"{name:30s} S={B:3d}   lock-step: p50 {rl['p50_ms']:.4f} p99 {rl['p99_ms']:.4f} ms   paced: p50 "
+                         f"{rp['p50_ms']:.4f} p99 {rp['p99_ms']:.4f} ms   paced minus lock-step {1e3 * cost:+.1f} us "
+                         f"({100.0 * cost / rl['p50_ms']:+.1f} %), scatter of the lock-step blocks "
+                         f"{1e3 * (max(p50s) - min(p50s)):.1f} us")
+        del lock, paced
+    if args.trace:
+        return
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--enroll", action="store_true")
+    ap.add_argument("--pace", action="store_true")
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--slots", type=int, default=64)
     ap.add_argument("--open", default="1,4,16,64")
@@ -230,7 +300,7 @@ def main():
     ap.add_argument("--steps", type=int, default=625)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--churn-every", type=int, default=25)
-    ap.add_argument("--trace", choices=["idle", "reset"], default=None)
+    ap.add_argument("--trace", choices=["idle", "reset", "held"], default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     net = Net(**config.TSH_PARAMS).eval()
@@ -240,6 +310,8 @@ def main():
         return enroll_bench(net, args)
     if args.compact:
         return compact_bench(net, args)
+    if args.pace:
+        return pace_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
