@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (19); bumped on any signature change. */
+/* ABI version of this header (20); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -480,7 +480,7 @@ int lh_metric_sums(const float* outputs, const float* target, const float* mixtu
 int lh_binaural_cues(const float* est, const float* gt, double* scratch, double* rows, double* sums, int B, int n_samples,
                      int sr, int frame, double rms_threshold, lh_stream_t stream);
 
-/* ---- streaming sessions (ABI 16 - 19) ----------------------------------------------------------------------------------------
+/* ---- streaming sessions (ABI 16 - 20) ----------------------------------------------------------------------------------------
  * A batched streaming host serves S listener SLOTS in lock-step (one 8 ms chunk of every slot per step; slot = batch row of
  * every streaming entry point above).  These two launches bracket the chunk's launch sequence — first and last node of a
  * captured per-chunk graph — and let slots open, close and fail one at a time, on the device and without a host wait (the
@@ -627,6 +627,58 @@ int lh_session_end_rows_paced(const lh_span_t* spans, int n_spans, const lh_span
                               lh_stream_t stream);
 int lh_session_capture_paced(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone,
                              const unsigned* hold, int n_chunks, int S, lh_stream_t stream);
+
+/* Suspend / resume (ABI 20): one listener's state leaves the buffers of a session host as bytes — a SNAPSHOT — and enters any
+ * row of any host of the same model: to park a listener who is away, to move one to another host or GPU, to keep a session
+ * across a restart.  Two launches that the host enqueues between two chunks (not nodes of a captured graph, and only in a step
+ * that suspends or resumes): both copy bytes, not numbers, with 16-byte loads and stores over a grid of (tile, section).
+ * Snapshot layout, every section at a multiple of 16 bytes, little endian, `snap` 16-byte aligned:
+ *   0     header, LH_SNAPSHOT_HEADER_BYTES = 64 words:  [0] LH_SNAPSHOT_MAGIC  [1] LH_SNAPSHOT_VERSION  [2] total bytes
+ *         [3] n_flat  [4] n_rings  [5] heads  [6] window  [7] embed_bytes  [8 ..) bytes of each flat span, then the row bytes
+ *         of each ring; the rest 0.  Written by lh_session_save from its own arguments.
+ *   256   words:  [0] active[row]  [1] cmd[1][row]  [2] ring position in [0, window)  [3] 0
+ *   272   the speaker embedding, embed_bytes
+ *   ...   the row's slice of flat span 0, 1, ..: the tails and (h, c) of the LIVE ping-pong set (the one the next chunk reads)
+ *   ...   ring 0, 1, ..: [heads][window][row bytes] — the window rows only, in ring order; the LH_KV_PAD_ROWS zero rows and the
+ *         dead ping-pong set are not part of a listener
+ * About 5.4 MB for the 3-block model against ~10 MB that a row occupies.
+ *   flat       host table like lh_session_begin's (validated here, travels in the launch arguments): n_flat in
+ *              [1, LH_SESSION_MAX_SPANS] tensors of which row r owns bytes [r * bytes, (r + 1) * bytes)
+ *   rings      host table of n_rings in [1, LH_SNAPSHOT_MAX_RINGS] K / V rings; `bytes` is the size of ONE ring row (a multiple
+ *              of 16).  Row r owns heads * ring_rows ring rows from row r * heads * ring_rows on, of which the first `window`
+ *              of every head are copied;  1 <= window <= ring_rows
+ *   embed      the listener's speaker embedding [embed_bytes], 16-byte aligned, embed_bytes a positive multiple of 16
+ *   cmd, active  the words of the bracket kernels, stride S;  row in [0, S)
+ * lh_session_save     reads row `row` and the device word `pos` — the row's own position of a paced host, the shared counter of
+ *              a lock-step one — and writes every byte of the layout.  The host's buffers are not written.
+ * lh_session_restore  writes the same sections into row `row` (the flat spans are those of the TARGET's live set), cmd[1][row]
+ *              from the snapshot, and the embedding; pad rows, the other rows and the dead set are untouched.  Exactly one of
+ *              pos_row / pos_shared is given.  pos_row (a paced target: the row's own position word): ring rows go back where
+ *              they were and *pos_row = the saved position — the raw order is what makes the continuation bit-identical.
+ *              pos_shared (a lock-step target: the shared counter, read only): ring row j goes to (j + delta) mod window with
+ *              delta = (*pos_shared - saved position) mod window, so the listener's oldest row is again the next one the
+ *              counter overwrites.  The host then opens the row with LH_SESSION_OPEN | generation and NO RESET: restore has
+ *              written every byte a RESET would zero that the chunk does not rewrite itself.
+ *              A DEAD snapshot — words[0] == 0: the device had closed the listener in the chunk before the save — must not come
+ *              alive: restore then overwrites the host's command cmd[0][row] with CLOSE | RESET and stores `gen`, the
+ *              generation of the opening the host has posted, to *fault (the slot's fault word, written like lh_session_end
+ *              does): the row is idle and zeroed, and the host learns of the fault as of any other.  Enqueue restore AFTER
+ *              the step's copy of the host's command words for that reason.  A non-zero words[0] with RESET in words[1] is a
+ *              paced listener opened and held who has consumed nothing: alive, the RESET travels and is served.
+ * State is only meaningful under the weights it was computed with; neither entry point can check that.
+ * LH_ERR_ARG: null or unaligned pointer, a table entry as for lh_session_begin, bad counts (n_flat + n_rings > 56, heads < 1,
+ * window outside [1, ring_rows]), row outside [0, S), snap_bytes smaller than the layout or the layout 2^31 bytes or more;
+ * restore: both or neither of pos_row / pos_shared, gen outside [1, 2^23).  Neither allocates, synchronises or reads device
+ * memory on the host. */
+enum { LH_SNAPSHOT_MAGIC = 0x5353484c /* "LHSS" */, LH_SNAPSHOT_VERSION = 1, LH_SNAPSHOT_HEADER_BYTES = 256,
+       LH_SNAPSHOT_MAX_RINGS = 8 };
+int lh_session_save(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads, int ring_rows,
+                    int window, const void* embed, int embed_bytes, void* snap, unsigned long long snap_bytes,
+                    const unsigned* cmd, const unsigned* active, const int* pos, int row, int S, lh_stream_t stream);
+int lh_session_restore(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads, int ring_rows,
+                       int window, void* embed, int embed_bytes, const void* snap, unsigned long long snap_bytes,
+                       unsigned* cmd, int* pos_row, const int* pos_shared, unsigned* fault, int gen, int row, int S,
+                       lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

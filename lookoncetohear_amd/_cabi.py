@@ -7,11 +7,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_double, c_int, c_void_p
+from ctypes import c_double, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -51,6 +51,9 @@ SIGNATURES = {
     "lh_session_begin_rows_paced": [_P, _I] + [_P] * 8 + [_I, _I, _P],
     "lh_session_end_rows_paced": [_P, _I, _P, _I] + [_P] * 10 + [_I, _I, _P],
     "lh_session_capture_paced": [_P] * 6 + [_I, _I, _P],
+    # suspend / resume (ABI 20): a listener's state out of / into a SessionStreamer's buffers, eager launches between two chunks
+    "lh_session_save": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, c_ulonglong, _P, _P, _P, _I, _I, _P],
+    "lh_session_restore": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, c_ulonglong, _P, _P, _P, _P, _I, _I, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)
@@ -172,6 +175,23 @@ class HipHost:
         """`n` zeroed 32-bit words in pinned host memory (see `_flag_words`; also the source of asynchronous copies)."""
         import torch
         return torch.zeros(n, dtype=torch.int32).pin_memory()
+
+    def _record_event(self, device):
+        """An event on the launch stream behind everything enqueued so far (a `SessionSnapshot` carries one)."""
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        return ev
+
+    def _wait_event(self, device, ev, tensor=None):
+        """Orders the launch stream behind `ev` — a stream wait, the host goes on — and tells the allocator that `tensor`
+        (allocated on the stream that recorded `ev`) is in use on this one."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        if ev is not None:
+            cur.wait_event(ev)
+        if tensor is not None and tensor.is_cuda:
+            tensor.record_stream(cur)
 
 
 def selftest_device(lib: "Lib", device_index: int) -> None:

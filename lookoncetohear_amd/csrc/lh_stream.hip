@@ -734,6 +734,155 @@ __global__ void __launch_bounds__(SC_NT) k_session_capture_paced(const float* __
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Suspend / resume (ABI 20): one listener's state out of the buffers as a snapshot, and back into any row of any host of the
+// same model (layout: include/lookonce_hip.h).  Not nodes of the per-chunk graph: the host enqueues them between two chunks,
+// and only in a step that suspends or resumes.  Copies like k_session_move — bytes, 16-byte loads and stores, a thread's SM_U
+// loads requested together before it stores any — over a grid of (tile, section): one section per flat span, one per ring,
+// and a last one (its tile 0 only) for the header, the words and the embedding.  A ring section is the `window` leading rows
+// of each of the row's heads: the snapshot holds them densely, [head][window row][row bytes], the ring has `rows` per head.
+// Who writes what: save writes the snapshot only.  Restore writes row `row`'s sections, cmd[1][row], the embedding, and in a
+// paced host the row's position word, which no other workgroup of the launch reads (there delta is 0 without looking); in a
+// lock-step host the shared counter is read by every workgroup and written by none.  The row is idle while restore runs.
+// ------------------------------------------------------------------------------------------------------
+struct SnapLayout { SessSpans flat, rings; int heads, rows, window; unsigned embed_bytes; };
+constexpr int SNAP_NT = SS_NT, SNAP_TILES = 32;
+constexpr unsigned SNAP_WORDS = LH_SNAPSHOT_HEADER_BYTES, SNAP_EMBED = SNAP_WORDS + 16;
+
+__host__ __device__ inline unsigned long long snap_ring_bytes(const SnapLayout& L, int i) {
+    return (unsigned long long)L.heads * L.window * L.rings.s[i].bytes;
+}
+// byte offset of section q: flat spans first, then the rings; q = n_flat + n_rings is the total
+__host__ __device__ inline unsigned long long snap_offset(const SnapLayout& L, int q) {
+    unsigned long long o = SNAP_EMBED + L.embed_bytes;
+    for (int i = 0; i < L.flat.n && i < q; ++i) o += L.flat.s[i].bytes;
+    for (int i = 0; i < L.rings.n && L.flat.n + i < q; ++i) o += snap_ring_bytes(L, i);
+    return o;
+}
+__device__ __forceinline__ unsigned snap_header_word(const SnapLayout& L, int i) {
+    const int nf = L.flat.n, nr = L.rings.n;
+    switch (i) {
+        case 0: return (unsigned)LH_SNAPSHOT_MAGIC;
+        case 1: return (unsigned)LH_SNAPSHOT_VERSION;
+        case 2: return (unsigned)snap_offset(L, nf + nr);
+        case 3: return (unsigned)nf;
+        case 4: return (unsigned)nr;
+        case 5: return (unsigned)L.heads;
+        case 6: return (unsigned)L.window;
+        case 7: return L.embed_bytes;
+        default: break;
+    }
+    if (i < 8 + nf) return (unsigned)L.flat.s[i - 8].bytes;
+    if (i < 8 + nf + nr) return (unsigned)L.rings.s[i - 8 - nf].bytes;
+    return 0u;
+}
+// this tile's share of n16 float4: dst[di(j)] = src[si(j)], j in [n16 tile / ntile, n16 (tile + 1) / ntile)
+template <class SI, class DI>
+__device__ __forceinline__ void snap_copy(const float4* __restrict__ src, float4* __restrict__ dst, long n16, int tile, int ntile,
+                                          int tid, SI si, DI di) {
+    const long hi = n16 * (tile + 1) / ntile;
+    for (long j = n16 * tile / ntile + tid; j < hi; j += (long)SM_U * SNAP_NT) {
+        float4 v[SM_U];
+#pragma unroll
+        for (int u = 0; u < SM_U; ++u) v[u] = src[si(min(j + (long)u * SNAP_NT, hi - 1))];
+#pragma unroll
+        for (int u = 0; u < SM_U; ++u)
+            if (j + (long)u * SNAP_NT < hi) dst[di(j + (long)u * SNAP_NT)] = v[u];
+    }
+}
+struct SnapDense { __device__ long operator()(long j) const { return j; } };
+// dense index j = (head, window row, float4 of the row) -> float4 index from the base of the row's ring rows; the window row is
+// rotated by `delta` in [0, window)
+struct SnapRing {
+    unsigned rb16, per_head, window, delta;
+    long head_stride;                              // float4 between two heads of the ring: rows * rb16
+    __device__ long operator()(long j) const {
+        const unsigned head = (unsigned)j / per_head, rem = (unsigned)j - head * per_head;
+        unsigned row = rem / rb16;
+        const unsigned col = rem - row * rb16;
+        row += delta;
+        if (row >= window) row -= window;
+        return (long)head * head_stride + (long)row * rb16 + col;
+    }
+};
+__device__ __forceinline__ SnapRing snap_ring(const SnapLayout& L, int i, unsigned delta) {
+    const unsigned rb16 = (unsigned)(L.rings.s[i].bytes >> 4);
+    return SnapRing{rb16, (unsigned)L.window * rb16, (unsigned)L.window, delta, (long)L.rows * rb16};
+}
+__device__ __forceinline__ int snap_wrap(int p, int window) {      // any word -> [0, window): a position never indexes past a ring
+    p %= window;
+    return p < 0 ? p + window : p;
+}
+
+// grid (SNAP_TILES, n_flat + n_rings + 1), block 256
+__global__ void __launch_bounds__(SNAP_NT) k_session_save(SnapLayout L, const float4* __restrict__ embed, char* __restrict__ snap,
+                                                          const unsigned* __restrict__ cmd, const unsigned* __restrict__ active,
+                                                          const int* __restrict__ pos, int row, int S) {
+    const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const int nf = L.flat.n, nr = L.rings.n;
+    if (q < nf) {
+        const lh_span_t sq = L.flat.s[q];
+        snap_copy(reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)row * sq.bytes),
+                  reinterpret_cast<float4*>(snap + snap_offset(L, q)), (long)(sq.bytes >> 4), tile, ntile, tid, SnapDense{},
+                  SnapDense{});
+    } else if (q < nf + nr) {
+        const int i = q - nf;
+        const SnapRing ring = snap_ring(L, i, 0u);
+        const float4* src = reinterpret_cast<const float4*>(L.rings.s[i].base) + (long)row * L.heads * ring.head_stride;
+        snap_copy(src, reinterpret_cast<float4*>(snap + snap_offset(L, q)), (long)L.heads * ring.per_head, tile, ntile, tid, ring,
+                  SnapDense{});
+    } else if (tile == 0) {
+        const unsigned a = active[row], c = cmd[S + row];
+        const int p = pos[0];
+        const int e16 = (int)(L.embed_bytes >> 4);
+        float4* pe = reinterpret_cast<float4*>(snap + SNAP_EMBED);
+        for (int j = tid; j < e16; j += SNAP_NT) pe[j] = embed[j];
+        if (tid == 0) {                            // 68 words by one lane, behind the other sections' 5 MB
+            unsigned* hw = reinterpret_cast<unsigned*>(snap);
+            for (int w = 0; w < LH_SNAPSHOT_HEADER_BYTES / 4; ++w) hw[w] = snap_header_word(L, w);
+            hw += SNAP_WORDS / 4;
+            hw[0] = a, hw[1] = c, hw[2] = (unsigned)snap_wrap(p, L.window), hw[3] = 0u;
+        }
+    }
+}
+
+// grid (SNAP_TILES, n_flat + n_rings + 1), block 256.  Exactly one of pos_row / pos_shared.
+__global__ void __launch_bounds__(SNAP_NT) k_session_restore(SnapLayout L, float4* __restrict__ embed, const char* __restrict__ snap,
+                                                             unsigned* cmd, int* pos_row, const int* __restrict__ pos_shared,
+                                                             unsigned* fault, unsigned gen, int row, int S) {
+    const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const int nf = L.flat.n, nr = L.rings.n;
+    const unsigned* words = reinterpret_cast<const unsigned*>(snap + SNAP_WORDS);
+    const unsigned was_active = words[0], was_cmd = words[1];
+    const int saved = snap_wrap((int)words[2], L.window);
+    if (q < nf) {
+        const lh_span_t sq = L.flat.s[q];
+        snap_copy(reinterpret_cast<const float4*>(snap + snap_offset(L, q)),
+                  reinterpret_cast<float4*>(static_cast<char*>(sq.base) + (unsigned long long)row * sq.bytes),
+                  (long)(sq.bytes >> 4), tile, ntile, tid, SnapDense{}, SnapDense{});
+    } else if (q < nf + nr) {
+        const int i = q - nf;
+        // a lock-step target: the listener's oldest row (at `saved`) becomes the row the shared counter overwrites next
+        const int delta = pos_shared ? snap_wrap(snap_wrap(pos_shared[0], L.window) - saved, L.window) : 0;
+        const SnapRing ring = snap_ring(L, i, (unsigned)delta);
+        float4* dst = reinterpret_cast<float4*>(L.rings.s[i].base) + (long)row * L.heads * ring.head_stride;
+        snap_copy(reinterpret_cast<const float4*>(snap + snap_offset(L, q)), dst, (long)L.heads * ring.per_head, tile, ntile, tid,
+                  SnapDense{}, ring);
+    } else if (tile == 0) {
+        const int e16 = (int)(L.embed_bytes >> 4);
+        const float4* pe = reinterpret_cast<const float4*>(snap + SNAP_EMBED);
+        for (int j = tid; j < e16; j += SNAP_NT) embed[j] = pe[j];
+        if (tid == 0) {
+            cmd[S + row] = was_cmd;
+            if (pos_row) pos_row[0] = saved;
+            if (was_active == 0u) {                   // a dead snapshot stays dead: the host's OPEN is taken back, the fault reported
+                cmd[row] = (unsigned)(LH_SESSION_CLOSE | LH_SESSION_RESET);
+                __hip_atomic_store(fault, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -935,5 +1084,58 @@ extern "C" int lh_session_capture_paced(const float* chunk_in, float* enroll, un
     if (((unsigned long long)(size_t)enroll & 15) || ((unsigned long long)(size_t)chunk_in & 15)) return LH_ERR_ARG;
     hipLaunchKernelGGL(k_session_capture_paced, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate,
                        edone, hold, n_chunks, S);
+    return check_launch();
+}
+
+// ---- suspend / resume (ABI 20) ----------------------------------------------------------------------------------------------
+namespace lh {
+static bool aligned16(const void* p) { return p && !((unsigned long long)(size_t)p & 15); }
+// the two tables, the ring geometry and the snapshot buffer of lh_session_save / lh_session_restore
+static bool snap_layout(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads, int ring_rows,
+                        int window, const void* embed, int embed_bytes, const void* snap, unsigned long long snap_bytes,
+                        int row, int S, SnapLayout& L) {
+    L = SnapLayout{};
+    if (!sess_spans(flat, n_flat, L.flat) || n_rings > LH_SNAPSHOT_MAX_RINGS || !sess_spans(rings, n_rings, L.rings)) return false;
+    if (8 + n_flat + n_rings > LH_SNAPSHOT_HEADER_BYTES / 4) return false;
+    if (heads < 1 || window < 1 || ring_rows < window || embed_bytes < 16 || (embed_bytes & 15)) return false;
+    if (!aligned16(embed) || !aligned16(snap) || S <= 0 || row < 0 || row >= S) return false;
+    L.heads = heads, L.rows = ring_rows, L.window = window, L.embed_bytes = (unsigned)embed_bytes;
+    unsigned long long total = SNAP_EMBED + L.embed_bytes;
+    for (int i = 0; i < n_flat; ++i) {
+        if (flat[i].bytes >> 31) return false;
+        total += flat[i].bytes;
+    }
+    for (int i = 0; i < n_rings; ++i) {
+        if (rings[i].bytes >> 31 || snap_ring_bytes(L, i) >> 31) return false;
+        total += snap_ring_bytes(L, i);
+    }
+    return total == snap_offset(L, n_flat + n_rings) && !(total >> 31) && snap_bytes >= total;
+}
+}  // namespace lh
+
+extern "C" int lh_session_save(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads, int ring_rows,
+                               int window, const void* embed, int embed_bytes, void* snap, unsigned long long snap_bytes,
+                               const unsigned* cmd, const unsigned* active, const int* pos, int row, int S, lh_stream_t stream) {
+    using namespace lh;
+    SnapLayout L;
+    if (!cmd || !active || !pos ||
+        !snap_layout(flat, n_flat, rings, n_rings, heads, ring_rows, window, embed, embed_bytes, snap, snap_bytes, row, S, L))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_save, dim3(SNAP_TILES, n_flat + n_rings + 1), dim3(SNAP_NT), 0, (hipStream_t)stream, L,
+                       (const float4*)embed, (char*)snap, cmd, active, pos, row, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_restore(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads,
+                                  int ring_rows, int window, void* embed, int embed_bytes, const void* snap,
+                                  unsigned long long snap_bytes, unsigned* cmd, int* pos_row, const int* pos_shared,
+                                  unsigned* fault, int gen, int row, int S, lh_stream_t stream) {
+    using namespace lh;
+    SnapLayout L;
+    if (!cmd || !fault || !pos_row == !pos_shared || gen < 1 || gen > 0x7fffff ||
+        !snap_layout(flat, n_flat, rings, n_rings, heads, ring_rows, window, embed, embed_bytes, snap, snap_bytes, row, S, L))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_restore, dim3(SNAP_TILES, n_flat + n_rings + 1), dim3(SNAP_NT), 0, (hipStream_t)stream, L,
+                       (float4*)embed, (const char*)snap, cmd, pos_row, pos_shared, fault, (unsigned)gen, row, S);
     return check_launch();
 }

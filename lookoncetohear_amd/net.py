@@ -1088,6 +1088,91 @@ class _Span(ctypes.Structure):
     _fields_ = [("base", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
 
 
+class SessionSnapshot:
+    """One listener's streaming state as a value: what `SessionStreamer.suspend` takes out and `resume` puts back, into any
+    slot of any `SessionStreamer` of the same model — after a minute, on another GPU, in another process.
+    `data`: ONE contiguous uint8 tensor in the layout of include/lookonce_hip.h ("suspend / resume"): header, the words, the
+    speaker embedding, the tails and (h, c) of the live ping-pong set, the 50 window rows per head of every K / V ring.
+    `event`: recorded behind the kernel that filled `data` (None for host memory, or where nothing is in flight); a resume on
+    another stream orders itself behind it with a stream wait.  `layout`: the header's sizes on the host, so that `resume`
+    can refuse a snapshot of another model without reading device memory.
+    A snapshot is never written after it was filled: it can be resumed any number of times.  The state is only meaningful
+    under the weights it was computed with; nothing checks that.  `to` never waits for the device; `cpu`, `save` and `load`
+    may: they are not for the chunk loop."""
+    MAGIC, VERSION, HEADER_BYTES = 0x5353484c, 1, 256       # LH_SNAPSHOT_*
+
+    def __init__(self, data: torch.Tensor, layout: tuple, event=None):
+        self.data, self.layout, self.event = data, tuple(layout), event
+
+    @staticmethod
+    def layout_bytes(layout: tuple) -> int:
+        """Size of a snapshot with these header sizes: (n_flat, n_rings, heads, window, embed_bytes, *flat, *ring rows)."""
+        n_flat, n_rings, heads, window, embed_bytes = layout[:5]
+        sizes = layout[5:]
+        return SessionSnapshot.HEADER_BYTES + 16 + embed_bytes + sum(sizes[:n_flat]) + heads * window * sum(sizes[n_flat:])
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def to(self, device) -> "SessionSnapshot":
+        """The snapshot in the memory of `device`: this object if it is there already, else a copy enqueued behind the event.
+        From device memory or pinned host memory (what `cpu` and `load` return where a GPU is present) the copy is asynchronous;
+        from pageable host memory it is staged and the host may wait for it."""
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if dev == self.data.device:
+            return self
+        if dev.type != "cuda":
+            return self.cpu()
+        if self.data.is_cuda:                               # the copy is issued on the source's current stream
+            cur = torch.cuda.current_stream(self.data.device)
+            if self.event is not None:
+                cur.wait_event(self.event)
+            self.data.record_stream(cur)
+        data = self.data.to(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        return SessionSnapshot(data, self.layout, ev)
+
+    def cpu(self) -> "SessionSnapshot":
+        """In host memory.  Waits for the kernel that fills the snapshot."""
+        if not self.data.is_cuda:
+            return self
+        if self.event is not None:
+            self.event.synchronize()
+        return SessionSnapshot(self._pinned(self.data.cpu()), self.layout, None)
+
+    @staticmethod
+    def _pinned(host: torch.Tensor) -> torch.Tensor:
+        """`host` in pinned memory where a GPU is present, so that a later `to(device)` does not stage the copy."""
+        return host.pin_memory() if torch.cuda.is_available() else host
+
+    def save(self, path: str):
+        """The bytes of `data` as a file: the header makes it self-describing."""
+        self.cpu().data.numpy().tofile(path)
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "SessionSnapshot":
+        """A snapshot from `save`'s file, in host memory or on `device`.  ValueError: not a snapshot, another layout version, or
+        a size that does not match the header."""
+        raw = np.fromfile(path, dtype=np.uint8)
+        if raw.size < cls.HEADER_BYTES + 16:
+            raise ValueError(f"{path}: {raw.size} bytes, not a session snapshot")
+        head = raw[:cls.HEADER_BYTES].view("<u4").astype(np.int64)
+        if head[0] != cls.MAGIC or head[1] != cls.VERSION:
+            raise ValueError(f"{path}: magic {int(head[0]):#x} version {int(head[1])}, expected {cls.MAGIC:#x} version {cls.VERSION}")
+        n_flat, n_rings = int(head[3]), int(head[4])
+        if n_flat < 1 or n_rings < 1 or 8 + n_flat + n_rings > cls.HEADER_BYTES // 4:
+            raise ValueError(f"{path}: header names {n_flat} state tensors and {n_rings} rings")
+        layout = tuple(int(v) for v in head[3:8 + n_flat + n_rings])
+        if cls.layout_bytes(layout) != raw.size or int(head[2]) != raw.size:
+            raise ValueError(f"{path}: {raw.size} bytes, the header's sizes make {cls.layout_bytes(layout)} (total word {int(head[2])})")
+        snap = cls(cls._pinned(torch.from_numpy(raw)), layout, None)
+        return snap if device is None else snap.to(device)
+
+
 class SessionStreamer:
     """A batched `Streamer` whose rows are listener SLOTS that open, close and fail one at a time.
 
@@ -1143,7 +1228,22 @@ class SessionStreamer:
     The hold words travel like the commands, a fresh pinned array copied asynchronously, and only in a step whose mask differs
     from the one on the device: a steady all-present loop copies nothing.  A held row costs what a live row costs — its
     kernels run on a zero-gated input and `lh_session_end_paced` puts the row's state back, about 0.2 MB of copies — so
-    pacing buys correctness under jitter, not time; a compacting streamer does not skip held rows."""
+    pacing buys correctness under jitter, not time; a compacting streamer does not skip held rows.
+    Suspend / resume (every flavour above, as source and as target, in any combination): `suspend(slot)` takes an open
+    listener's state, as of the last `step`, out as a `SessionSnapshot` — one launch (`lh_session_save`) into a fresh device
+    tensor: the tails and (h, c) of the ping-pong set the next chunk would read, the 50 window rows per head of every ring, the
+    ring position (the row's own, or the shared counter), the speaker embedding and the row's two device words — and closes the
+    slot.  `resume(slot, snapshot)` makes an idle slot that listener again from the next `step` on: `step` enqueues
+    `lh_session_restore` behind its copy of the command words and ahead of the chunk (eager launches between two replays,
+    like `set_embedding`'s; the graphs are what they were), and the slot opens WITHOUT a reset.  Into a paced streamer the ring
+    rows and the position go back as they were, and the listener's output continues bit for bit; into a lock-step streamer the
+    ring rows are rotated so that the listener's oldest row is the next one the shared counter overwrites — bit for bit when
+    the shared position equals the saved one, within the tolerance of a listener opened at an arbitrary position otherwise.
+    A compacting streamer plans a resume as an opening: it takes a hole, which no move of that step reads or writes; a slot
+    closed or suspended and resumed between two steps gives its previous listener's row up first, like any listener that left.  A
+    listener the device had closed in the chunk before `suspend` (the fault word not yet seen) makes a dead snapshot: resuming
+    it leaves the slot idle on the device and lists it in `faults()` after that `step`.  Neither call waits for the device.
+    A snapshot is only meaningful under the weights it was taken with: that is the caller's to keep."""
     RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
     ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
 
@@ -1197,6 +1297,17 @@ class SessionStreamer:
         # what chunk k WRITES: the (h, c) of the other ping-pong set
         self._spans_end = [(_Span * (2 * net.n_blocks))(*[span(t) for t in st.sets[k ^ 1]["h"] + st.sets[k ^ 1]["c"]])
                            for k in (0, 1)]
+        # suspend / resume: the tails and (h, c) of each ping-pong set, the rings with their geometry, the snapshot's sizes
+        tails = lambda x: [x["conv_buf"], x["deconv_buf"], x["istft_buf"]] + x["h"] + x["c"]
+        rings = [t for kv in st.rings for t in kv]
+        self._spans_live = [(_Span * len(tails(x)))(*[span(t) for t in tails(x)]) for x in st.sets]
+        self._spans_rings = (_Span * len(rings))(*[_Span(t.data_ptr(), t.shape[-1] * t.element_size()) for t in rings])
+        self._ring_geom = (net.n_head, rings[0].shape[1], net.local_atten_len)      # heads per slot, rows per head, window
+        self._snap_layout = (len(self._spans_live[0]), len(rings), net.n_head, net.local_atten_len,
+                             st.embed.shape[1] * st.embed.element_size(), *[sp.bytes for sp in self._spans_live[0]],
+                             *[sp.bytes for sp in self._spans_rings])
+        self._snap_bytes = SessionSnapshot.layout_bytes(self._snap_layout)
+        self._resumes = {}                                  # slot -> [snapshot, embedding set since `resume` or None]
         self.pace = bool(pace)
         if pace:
             self._ring = torch.zeros(2, S, dtype=torch.int32, device=dev)    # per row: ring position | the chunk's write slot
@@ -1326,6 +1437,7 @@ class SessionStreamer:
         self._fault.zero_()
         self._gen = [0] * self.S
         self._pending.clear()
+        self._resumes.clear()
         if self.enroll_chunks:
             self._ewords.zero_()
             self._edone.zero_()
@@ -1408,7 +1520,10 @@ class SessionStreamer:
         row_of, slot_of, n_old = self._row_of, self._slot_of, self._n_rows
         for r in range(n_old):                              # closed by the host, or by the device and seen now
             s = slot_of[r]
-            if not gen[s] or int(f[s]) == gen[s]:
+            # ... or closed / suspended and resumed since the last step: the row is the PREVIOUS listener's.  It is given up
+            # like theirs, so that the resume is an opening and takes a hole — a row kept here could be a mover of this step,
+            # and the move would copy the previous listener over what `_restore` has written
+            if not gen[s] or int(f[s]) == gen[s] or s in self._resumes:
                 slot_of[r], row_of[s] = -1, -1
         opens = [s for s, w in pend.items() if w & self.OPEN and row_of[s] < 0]
         keep = [r for r in range(n_old) if slot_of[r] >= 0]
@@ -1423,7 +1538,8 @@ class SessionStreamer:
             words[0, dst] = r + 1
         for s, dst in zip(opens, holes[len(movers):]):
             slot_of[dst], row_of[s] = s, dst
-            self._row_gain(s, dst)                          # a hole or a new row: never the source of a move
+            if s not in self._resumes:                      # a resumed listener's gain follows their embedding: `_restore`
+                self._row_gain(s, dst)                      # a hole or a new row: never the source of a move
         words[1], words[2] = slot_of, row_of
         for s, w in pend.items():
             if w & self.OPEN:                               # a row whose listener left needs no word: it has no slot
@@ -1491,13 +1607,89 @@ class SessionStreamer:
             raise ValueError(f"slot {slot} is not open")
         self._gen[slot] = 0
         self._enrolled.pop(slot, None)
+        self._resumes.pop(slot, None)                       # resumed and closed before a `step`: nothing is restored
         self._pending[slot] = self.RESET | self.CLOSE
+
+    def _snap_args(self, k: int, slot: int):
+        """The leading arguments of lh_session_save / lh_session_restore up to the embedding: ping-pong set k, `slot`."""
+        live, rings, emb = self._spans_live[k], self._spans_rings, self._st.embed
+        return (ctypes.addressof(live), len(live), ctypes.addressof(rings), len(rings), *self._ring_geom,
+                emb[slot].data_ptr(), emb.shape[1] * emb.element_size())
+
+    def suspend(self, slot: int) -> SessionSnapshot:
+        """The listener of open `slot` as a `SessionSnapshot`: their state as of the last `step`.  From the next `step` on the
+        slot is idle exactly as after `close(slot)`.  Enqueues one launch and returns; never waits for the device."""
+        self._slot(slot)
+        if slot in self._capturing or slot in self._embedding:
+            raise ValueError(f"slot {slot} is enrolling: it has no session yet")
+        if slot not in self.active:
+            raise ValueError(f"slot {slot} is not open")
+        if slot in self._pending:
+            raise ValueError(f"slot {slot} was opened or resumed and no step has served it yet: it has no state on the device")
+        st, net, S = self._st, self.net, self.S
+        row = self._row_of[slot] if self.compact else slot
+        words = self._tables[3:] if self.compact else self._words       # cmd from the host | cmd from the device | active
+        pos = self._ring[0, row:row + 1] if self.pace else st.pos       # the word that holds this row's ring position
+        data = torch.empty(self._snap_bytes, dtype=torch.uint8, device=self.device)
+        with torch.no_grad(), net._device_ctx(st.chunk):
+            # the set the next chunk reads is the one the last chunk wrote: sets[parity]
+            net._lib(st.chunk).call("lh_session_save", *self._snap_args(st.parity, slot), data.data_ptr(), self._snap_bytes,
+                                    words.data_ptr(), words[2].data_ptr(), pos.data_ptr(), row, S, net._stream(self.device))
+            event = net._record_event(self.device)
+        self._gen[slot] = 0
+        self._enrolled.pop(slot, None)
+        self._pending[slot] = self.RESET | self.CLOSE
+        return SessionSnapshot(data, self._snap_layout, event)
+
+    def resume(self, slot: int, snapshot: SessionSnapshot):
+        """From the next `step` on idle `slot` is the listener of `snapshot`: carried state, ring history, ring position and
+        speaker embedding are theirs (there is no embedding argument).  ValueError for a snapshot of another model layout.
+        Never waits for the device: a snapshot in another GPU's memory is copied over behind its event."""
+        self._slot(slot)
+        if slot in self.active:
+            raise ValueError(f"slot {slot} is open: close() it first")
+        if slot in self._capturing or slot in self._embedding:
+            self.poll()                                     # an aborted capture has left the slot idle
+            if slot in self._capturing or slot in self._embedding:
+                raise ValueError(f"slot {slot} is enrolling: close() it first")
+        if snapshot.layout != self._snap_layout or snapshot.data.numel() != self._snap_bytes:
+            raise ValueError(f"the snapshot's layout {snapshot.layout} ({snapshot.data.numel()} bytes) is not this Net's "
+                             f"{self._snap_layout} ({self._snap_bytes} bytes)")
+        self._enroll_faults.discard(slot)
+        self._enrolled.pop(slot, None)
+        gen = self._new_gen()
+        self._gen[slot] = gen
+        # no RESET: lh_session_restore writes every byte a RESET would zero, apart from what the chunk rewrites itself
+        self._pending[slot] = self.OPEN | (gen << self.GEN_SHIFT)
+        self._resumes[slot] = [snapshot.to(self.device), None]
+
+    def _restore(self):
+        """The resumes of this step, behind the copy of the command words (a dead snapshot takes its OPEN back) and ahead of
+        the chunk.  The rows are idle, and in a compacting streamer holes: no move of the step reads or writes them."""
+        st, net, S = self._st, self.net, self.S
+        words = self._tables[3:] if self.compact else self._words
+        with torch.no_grad(), net._device_ctx(st.chunk):
+            lib, stream = net._lib(st.chunk), net._stream(self.device)
+            for slot, (snap, embed) in self._resumes.items():
+                row = self._row_of[slot] if self.compact else slot
+                net._wait_event(self.device, snap.event, snap.data)
+                pos_row, pos_shared = (self._ring[0, row:row + 1].data_ptr(), None) if self.pace else (None, st.pos.data_ptr())
+                lib.call("lh_session_restore", *self._snap_args(st.parity, slot), snap.data.data_ptr(), snap.data.numel(),
+                         words.data_ptr(), pos_row, pos_shared, self._fault[slot:slot + 1].data_ptr(), self._gen[slot], row, S,
+                         stream)
+                if embed is not None:                       # `set_embedding` after `resume`
+                    st.embed[slot].copy_(embed.reshape(-1), non_blocking=True)
+                self._row_gain(slot, row)
+        self._resumes.clear()
 
     def set_embedding(self, slot: int, embed: torch.Tensor):
         """Re-target an open slot ("look once" at another speaker): the carried state is kept."""
         self._slot(slot)
         if not self._gen[slot]:
             raise ValueError(f"slot {slot} is not open")
+        if slot in self._resumes:                           # the snapshot's embedding is not there yet: after the restore
+            self._resumes[slot][1] = embed
+            return
         self._set_gain(slot, embed)
 
     def poll(self):
@@ -1574,6 +1766,8 @@ class SessionStreamer:
                 words[slot] = w
             self._epending.clear()
             self._ewords[0].copy_(src, non_blocking=True)
+        if self._resumes:
+            self._restore()
         self.chunk_in.copy_(chunks)
         with torch.no_grad():
             if self.graphs is None:

@@ -22,6 +22,11 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         mask that changes in every step, which is the path that copies the hold words.
     python scripts/bench_sessions.py --pace --trace idle|held --batches 64   # the short loop for rocprofv3, as above:
         idle = everyone present; held = every second slot held
+    python scripts/bench_sessions.py --suspend [--batches 1,64] [--move-reps 20] [--out profiles/xyz.txt]
+        what suspend / resume costs, in DEVICE time per chunk as above (the events enclose the call and the step it precedes), in
+        a paced streamer with every slot open: a step that suspends one listener and, three steps later, a step that resumes
+        them, against the steady steps of the same streamer in the same interleaved run; at the largest batch also the park
+        and return of 8 listeners at once.  `scatter` is the spread of the steady blocks' p50.
 """
 import argparse
 import json
@@ -287,11 +292,66 @@ def pace_bench(net, args):
             f.write(text + "\n")
 
 
+def suspend_bench(net, args):
+    def timed_step(ss, chunk, action=None):
+        """One step in device time; `action` (the suspends or resumes of the step) is enqueued inside the interval."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if action is not None:
+            action()
+        ss.step(chunk)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    lines = [f"suspend / resume cost, device time per chunk (HIP events around the call and the replay), paced streamer, every "
+             f"slot open, {args.move_reps} cycles of 12 steady steps, a step that suspends, 3 steps, a step that resumes"]
+    batches = [int(b) for b in args.batches.split(",")]
+    for B in batches:
+        d = synth.batch(list(range(B)), 80000)
+        mix = torch.nn.functional.pad(d["mixture"], (0, 64)).to(DEV)
+        emb = d["embedding_gt"][:, 0].to(DEV)
+        chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+        ss = net.make_session_streamer(B, DEV, pace=True)
+        for s in range(B):
+            ss.open(s, emb[s])
+        dev_steps(ss, chunks, 0, args.warmup)
+        for m in ([1, 8] if B == max(batches) and B >= 8 else [1]):
+            steady, p50s, park, back, i, snaps = [], [], [], [], 0, []
+            for rep in range(args.move_reps):
+                blk = [timed_step(ss, chunks[(i + j) % 625]) for j in range(12)][4:]
+                steady += blk
+                p50s.append(pct(blk, 0.5))
+                park.append(timed_step(ss, chunks[(i + 12) % 625], lambda: snaps.extend(ss.suspend(s) for s in range(m))))
+                for j in range(3):
+                    timed_step(ss, chunks[(i + 13 + j) % 625])
+                back.append(timed_step(ss, chunks[(i + 16) % 625], lambda: [ss.resume(s, snaps.pop(0)) for s in range(m)]))
+                i += 17
+            torch.cuda.synchronize()
+            assert ss.faults() == [] and len(ss.active) == B and not snaps
+            rs, scatter = stats(steady), max(p50s) - min(p50s)
+            for name, ms in (("suspends", park), ("resumes", back)):
+                r = stats(ms)
+                cost = r["p50_ms"] - rs["p50_ms"]
+                lines.append(f"S={B:3d} a step that {name} {m} listener{'s' if m > 1 else ' '} ({r['n']} times, "
+                             f"{m * ss._snap_bytes / 1e6:.1f} MB of snapshots): p50 {r['p50_ms']:.4f} max {r['max_ms']:.4f} ms   "
+                             f"steady steps: p50 {rs['p50_ms']:.4f} p99 {rs['p99_ms']:.4f} ms   p50 cost {1e3 * cost:+.1f} us, "
+                             f"scatter of the steady blocks {1e3 * scatter:.1f} us: "
+                             f"{'WITHIN' if cost <= 3 * scatter else 'NOT within'} three times the scatter")
+        del ss
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--enroll", action="store_true")
     ap.add_argument("--pace", action="store_true")
     ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--suspend", action="store_true")
     ap.add_argument("--slots", type=int, default=64)
     ap.add_argument("--open", default="1,4,16,64")
     ap.add_argument("--move-reps", type=int, default=20)
@@ -312,6 +372,8 @@ def main():
         return compact_bench(net, args)
     if args.pace:
         return pace_bench(net, args)
+    if args.suspend:
+        return suspend_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
