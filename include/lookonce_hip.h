@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (20); bumped on any signature change. */
+/* ABI version of this header (21); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -679,6 +679,43 @@ int lh_session_restore(const lh_span_t* flat, int n_flat, const lh_span_t* rings
                        int window, void* embed, int embed_bytes, const void* snap, unsigned long long snap_bytes,
                        unsigned* cmd, int* pos_row, const int* pos_shared, unsigned* fault, int gen, int row, int S,
                        lh_stream_t stream);
+
+/* Suspend / resume of many listeners (ABI 21): the two launches above for any number of listeners at once — draining a GPU,
+ * rebalancing, adopting another host's listeners between two chunks.  ONE launch each, whatever n_items is: the grid is
+ * (tile, section, item).  The single forms are what they were.  Arguments as above, except:
+ *   items      table of n_items entries in DEVICE memory (4-byte aligned), n_items in [1, S].  Item i acts on row items[i].row,
+ *              whose listener is slot items[i].slot; its snapshot lies at snaps + items[i].index * snap_stride; `gen` (restore
+ *              only) is the generation of the opening the host has posted for the slot, what the single form takes as `gen`.
+ *              The host hands out distinct rows and slots (and, for save, distinct indexes); restore may name any subset of a
+ *              buffer's snapshots.  On the device an item whose row or slot is outside [0, S) or whose index is negative is
+ *              skipped whole, by every workgroup, before an address is formed; that `index` stays inside the caller's buffer is
+ *              the caller's to keep — the entry points do not know its size.
+ *   snaps, snap_stride   a [.][snap_stride] buffer, 16-byte aligned, snap_stride a multiple of 16 and at least the layout's
+ *              bytes.  Save writes the first `layout` bytes of a snapshot — byte for byte what lh_session_save writes for that
+ *              row — and not the padding up to snap_stride.
+ *   embed      [S][embed_bytes], by SLOT (the single forms take the listener's own).   fault  [S] by slot.
+ *   pos_rows / pos_shared   exactly one.  pos_rows: [S] by row, a paced host's position words — save reads, restore writes
+ *              pos_rows[row].  pos_shared: a lock-step host's counter — read by both; restore rotates every item by its own
+ *              delta = (*pos_shared - its saved position) mod window.
+ * Tiles per (item, section): 32, as in the single forms, for any n_items (measured flat from 4 to 64 tiles with 64 listeners
+ * in flight, profiles/suspend_many_cost.txt); lh_set_tuning(18, n) sets another count for A/B runs, 0 = 32.
+ * lh_embed_proj_ln_rows: lh_embed_proj_ln for the rows of such a table, in the same two kernels whatever n_items is —
+ * gain[items[i].row] from embed[items[i].slot], both [S][.]; scratch [S][6208] by row.  A row's bits are those of
+ * lh_embed_proj_ln on that row alone.  Items outside [0, S) are skipped; `index` and `gen` are not looked at.
+ * LH_ERR_ARG: what the single forms refuse, n_items outside [1, S], a null or misaligned items, snap_stride smaller than the
+ * layout or not a multiple of 16, both or neither of pos_rows / pos_shared.  None allocates, synchronises or reads device
+ * memory on the host. */
+typedef struct { int row; int slot; unsigned gen; int index; } lh_snap_item_t;   /* 16 bytes */
+int lh_session_save_rows(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads, int ring_rows,
+                         int window, const void* embed, int embed_bytes, void* snaps, unsigned long long snap_stride,
+                         const unsigned* cmd, const unsigned* active, const int* pos_rows, const int* pos_shared,
+                         const lh_snap_item_t* items, int n_items, int S, lh_stream_t stream);
+int lh_session_restore_rows(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads, int ring_rows,
+                            int window, void* embed, int embed_bytes, const void* snaps, unsigned long long snap_stride,
+                            unsigned* cmd, int* pos_rows, const int* pos_shared, unsigned* fault, const lh_snap_item_t* items,
+                            int n_items, int S, lh_stream_t stream);
+int lh_embed_proj_ln_rows(const float* embed, const float* w, const float* bias, const float* ln_w, const float* ln_b,
+                          float* scratch, float* gain, const lh_snap_item_t* items, int n_items, int S, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

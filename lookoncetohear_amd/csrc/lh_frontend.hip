@@ -198,14 +198,35 @@ __global__ void __launch_bounds__(FE_NTH, 1) k_stft_conv_in(const float* __restr
 // speaker-gain projection, row-parallel: grid (ceil(6208/32), ceil(B/8)); each workgroup streams 32 rows of W once
 // and applies them to 8 utterances (W is read from HBM once per launch, re-used from L2 across the batch groups)
 constexpr int EP_ROWS = 32, EP_NB = 8;
-__global__ void __launch_bounds__(256) k_embed_proj(const float* __restrict__ emb, const float* __restrict__ w,
-                                                     const float* __restrict__ bias, float* __restrict__ raw, int B) {
+// ROWS (lh_embed_proj_ln_rows): utterance b is item b of a table in device memory — the embedding of items[b].slot, the
+// projection and the gain of items[b].row; an item outside [0, S) reads row 0 and writes nothing.  The arithmetic of a row is
+// the same instructions either way: a row's bits do not depend on the form or on the batch around it.
+__device__ __forceinline__ bool embed_item(const lh_snap_item_t* __restrict__ items, int b, int S, int& row, int& slot) {
+    const lh_snap_item_t it = items[b];
+    row = it.row, slot = it.slot;
+    return (unsigned)it.row < (unsigned)S && (unsigned)it.slot < (unsigned)S;
+}
+template <bool ROWS>
+__device__ __forceinline__ void embed_proj_body(const float* __restrict__ emb, const float* __restrict__ w,
+                                                const float* __restrict__ bias, float* __restrict__ raw, int B,
+                                                const lh_snap_item_t* __restrict__ items, int S) {
     constexpr int N = C * NF;
     __shared__ __attribute__((aligned(16))) float es[EP_NB][SPK];
+    __shared__ int out_row[EP_NB];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(tid);
     const int b0 = blockIdx.y * EP_NB;
+    if constexpr (ROWS) {
+        if (tid < EP_NB) {
+            int row = 0, slot = 0;
+            out_row[tid] = b0 + tid < B && embed_item(items, b0 + tid, S, row, slot) ? row : -1;
+        }
+    }
     for (int i = tid; i < EP_NB * SPK; i += 256) {
-        const int bb = min(b0 + i / SPK, B - 1);
+        int bb = min(b0 + i / SPK, B - 1);
+        if constexpr (ROWS) {
+            int row, slot;
+            bb = embed_item(items, bb, S, row, slot) ? slot : 0;
+        }
         es[i / SPK][i % SPK] = emb[(long)bb * SPK + (i % SPK)];
     }
     __syncthreads();
@@ -228,19 +249,31 @@ __global__ void __launch_bounds__(256) k_embed_proj(const float* __restrict__ em
         for (int j = 0; j < EP_NB; ++j) {
             const float4 e4 = *reinterpret_cast<const float4*>(&es[j][lane * 4]);
             float s = wave_sum(w4[q].x * e4.x + w4[q].y * e4.y + w4[q].z * e4.z + w4[q].w * e4.w);
-            if (lane == 0 && b0 + j < B) raw[(long)(b0 + j) * N + r] = s + bz[q];
+            if constexpr (ROWS) {
+                if (lane == 0 && out_row[j] >= 0) raw[(long)out_row[j] * N + r] = s + bz[q];
+            } else {
+                if (lane == 0 && b0 + j < B) raw[(long)(b0 + j) * N + r] = s + bz[q];
+            }
         }
     }
 }
+__global__ void __launch_bounds__(256) k_embed_proj(const float* __restrict__ emb, const float* __restrict__ w,
+                                                     const float* __restrict__ bias, float* __restrict__ raw, int B) {
+    embed_proj_body<false>(emb, w, bias, raw, B, nullptr, 0);
+}
+__global__ void __launch_bounds__(256) k_embed_proj_rows(const float* __restrict__ emb, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, float* __restrict__ raw,
+                                                          const lh_snap_item_t* __restrict__ items, int B, int S) {
+    embed_proj_body<true>(emb, w, bias, raw, B, items, S);
+}
 
-// LayerNorm over the 6208 projected values of one utterance + (c,f) -> (f,c) transpose; grid B
-__global__ void __launch_bounds__(256) k_embed_ln(const float* __restrict__ raw, const float* __restrict__ lnw,
-                                                   const float* __restrict__ lnb, float* __restrict__ gain) {
+// LayerNorm over the 6208 projected values of one utterance + (c,f) -> (f,c) transpose; grid B.  `b`: the row of raw and gain
+__device__ __forceinline__ void embed_ln_body(const float* __restrict__ raw, const float* __restrict__ lnw,
+                                              const float* __restrict__ lnb, float* __restrict__ gain, int b) {
     constexpr int N = C * NF;   // 6208
     __shared__ float vals[N];
     __shared__ float red[4];
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
     float s = 0.0f;
     for (int i = tid; i < N; i += 256) { const float v = raw[(long)b * N + i]; vals[i] = v; s += v; }
     const float mean = block_sum_256(s, red) * (1.0f / N);
@@ -254,6 +287,17 @@ __global__ void __launch_bounds__(256) k_embed_ln(const float* __restrict__ raw,
         const int i = c * NF + f;                     // reference flat order is channel-major (reshape [B,C,F])
         gain[(long)b * N + oidx] = (vals[i] - mean) * rstd * lnw[i] + lnb[i];
     }
+}
+__global__ void __launch_bounds__(256) k_embed_ln(const float* __restrict__ raw, const float* __restrict__ lnw,
+                                                   const float* __restrict__ lnb, float* __restrict__ gain) {
+    embed_ln_body(raw, lnw, lnb, gain, blockIdx.x);
+}
+__global__ void __launch_bounds__(256) k_embed_ln_rows(const float* __restrict__ raw, const float* __restrict__ lnw,
+                                                        const float* __restrict__ lnb, float* __restrict__ gain,
+                                                        const lh_snap_item_t* __restrict__ items, int S) {
+    int row, slot;
+    if (!embed_item(items, blockIdx.x, S, row, slot)) return;
+    embed_ln_body(raw, lnw, lnb, gain, row);
 }
 
 }  // namespace lh
@@ -281,7 +325,21 @@ extern "C" int lh_embed_proj_ln(const float* emb, const float* w, const float* b
     return check_launch();
 }
 
-extern "C" int lh_abi_version(void) { return 20; }
+// the speaker gains of the rows a step resumes (ABI 21): embed [S][256] by slot -> scratch, gain [S][6208] by row
+extern "C" int lh_embed_proj_ln_rows(const float* embed, const float* w, const float* bias, const float* ln_w,
+                                     const float* ln_b, float* scratch, float* gain, const lh_snap_item_t* items, int n_items,
+                                     int S, lh_stream_t stream) {
+    using namespace lh;
+    if (!embed || !w || !bias || !ln_w || !ln_b || !scratch || !gain || scratch == gain || !items || S <= 0 || n_items < 1 ||
+        n_items > S)
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_embed_proj_rows, dim3((C * NF + EP_ROWS - 1) / EP_ROWS, (n_items + EP_NB - 1) / EP_NB), dim3(256), 0,
+                       (hipStream_t)stream, embed, w, bias, scratch, items, n_items, S);
+    hipLaunchKernelGGL(k_embed_ln_rows, dim3(n_items), dim3(256), 0, (hipStream_t)stream, scratch, ln_w, ln_b, gain, items, S);
+    return check_launch();
+}
+
+extern "C" int lh_abi_version(void) { return 21; }
 
 extern "C" int lh_check_config(int nfft, int hop, int n_mics, int emb_dim, int n_blocks_unused, int lstm_hidden,
                                int n_heads, int attn_window, int n_srcs, int spk_emb_dim) {

@@ -1049,6 +1049,7 @@ int launch_inter_xp(const float* x, const void* w_pk, const float* b_sum, const 
                     int si, int ps, hipStream_t st, int cflags = 0);
 }
 namespace lh { int backend_set_runs(int v); } // lh_backend.hip
+namespace lh { int snap_set_tiles(int v); }   // lh_stream.hip
 #if defined(LH_PROBE_TRACE)
 extern "C" int lh_probe_trace_read(unsigned long long* host_dst) {
     return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(lh::lh_trace_buf), sizeof(lh::lh_trace_buf)) == hipSuccess ? 0 : 1;
@@ -1059,6 +1060,7 @@ extern "C" int lh_set_tuning(int key, int value) {
     if (key == 6) return lh::backend_set_runs(value);
     if (key >= 7 && key < 16) return lh::xp_set(key, value);      // lh_recur.hip switches
     if (key == 16 || key == 17) return lh::emb_set(key, value);   // lh_embed.hip: k_emb_rec issue priority, attention GEMM variant
+    if (key == 18) return lh::snap_set_tiles(value);              // lh_stream.hip: tiles per item of the *_rows snapshot kernels
     if (key < 0 || key >= 8) return LH_ERR_ARG;
 #if defined(LH_LEGACY)
     if (key == 3) lh::g_dephase = value;

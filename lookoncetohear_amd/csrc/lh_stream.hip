@@ -883,6 +883,101 @@ __global__ void __launch_bounds__(SNAP_NT) k_session_restore(SnapLayout L, float
     }
 }
 
+// Suspend / resume of many listeners (ABI 21): the two kernels above with the listener as a third grid dimension and a table in
+// device memory that says, per item, which row, whose slot, which snapshot of a [.][stride] buffer.  The same sections, the same
+// copy (snap_copy, the layout helpers), the same words; embed, fault and the position words are BASES here, indexed by slot,
+// slot and row.  An item whose row or slot is outside [0, S) or whose index is negative is skipped by all of its workgroups
+// before any address is formed.  The host hands out distinct rows, slots and (for save) indexes: the workgroups of two items
+// share nothing but the read-only shared counter.
+struct SnapItem { int row, slot, index; unsigned gen; bool ok; };
+__device__ __forceinline__ SnapItem snap_item(const lh_snap_item_t* __restrict__ items, int i, int S) {
+    const lh_snap_item_t it = items[i];
+    return SnapItem{it.row, it.slot, it.index, it.gen,
+                    (unsigned)it.row < (unsigned)S && (unsigned)it.slot < (unsigned)S && it.index >= 0};
+}
+
+// grid (tiles, n_flat + n_rings + 1, n_items), block 256.  Exactly one of pos_rows / pos_shared.
+__global__ void __launch_bounds__(SNAP_NT) k_session_save_rows(SnapLayout L, const char* __restrict__ embed, char* __restrict__ snaps,
+                                                               unsigned long long stride, const unsigned* __restrict__ cmd,
+                                                               const unsigned* __restrict__ active,
+                                                               const int* __restrict__ pos_rows, const int* __restrict__ pos_shared,
+                                                               const lh_snap_item_t* __restrict__ items, int S) {
+    const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const int nf = L.flat.n, nr = L.rings.n;
+    const SnapItem it = snap_item(items, blockIdx.z, S);
+    if (!it.ok) return;
+    const int row = it.row;
+    char* snap = snaps + (unsigned long long)it.index * stride;
+    if (q < nf) {
+        const lh_span_t sq = L.flat.s[q];
+        snap_copy(reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)row * sq.bytes),
+                  reinterpret_cast<float4*>(snap + snap_offset(L, q)), (long)(sq.bytes >> 4), tile, ntile, tid, SnapDense{},
+                  SnapDense{});
+    } else if (q < nf + nr) {
+        const int i = q - nf;
+        const SnapRing ring = snap_ring(L, i, 0u);
+        const float4* src = reinterpret_cast<const float4*>(L.rings.s[i].base) + (long)row * L.heads * ring.head_stride;
+        snap_copy(src, reinterpret_cast<float4*>(snap + snap_offset(L, q)), (long)L.heads * ring.per_head, tile, ntile, tid, ring,
+                  SnapDense{});
+    } else if (tile == 0) {
+        const unsigned a = active[row], c = cmd[S + row];
+        const int p = pos_rows ? pos_rows[row] : pos_shared[0];
+        const int e16 = (int)(L.embed_bytes >> 4);
+        const float4* se = reinterpret_cast<const float4*>(embed + (unsigned long long)it.slot * L.embed_bytes);
+        float4* pe = reinterpret_cast<float4*>(snap + SNAP_EMBED);
+        for (int j = tid; j < e16; j += SNAP_NT) pe[j] = se[j];
+        if (tid == 0) {
+            unsigned* hw = reinterpret_cast<unsigned*>(snap);
+            for (int w = 0; w < LH_SNAPSHOT_HEADER_BYTES / 4; ++w) hw[w] = snap_header_word(L, w);
+            hw += SNAP_WORDS / 4;
+            hw[0] = a, hw[1] = c, hw[2] = (unsigned)snap_wrap(p, L.window), hw[3] = 0u;
+        }
+    }
+}
+
+// grid (tiles, n_flat + n_rings + 1, n_items), block 256.  Exactly one of pos_rows / pos_shared.
+__global__ void __launch_bounds__(SNAP_NT) k_session_restore_rows(SnapLayout L, char* __restrict__ embed,
+                                                                  const char* __restrict__ snaps, unsigned long long stride,
+                                                                  unsigned* cmd, int* pos_rows, const int* __restrict__ pos_shared,
+                                                                  unsigned* fault, const lh_snap_item_t* __restrict__ items, int S) {
+    const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const int nf = L.flat.n, nr = L.rings.n;
+    const SnapItem it = snap_item(items, blockIdx.z, S);
+    if (!it.ok) return;
+    const int row = it.row;
+    const char* snap = snaps + (unsigned long long)it.index * stride;
+    const unsigned* words = reinterpret_cast<const unsigned*>(snap + SNAP_WORDS);
+    const unsigned was_active = words[0], was_cmd = words[1];
+    const int saved = snap_wrap((int)words[2], L.window);
+    if (q < nf) {
+        const lh_span_t sq = L.flat.s[q];
+        snap_copy(reinterpret_cast<const float4*>(snap + snap_offset(L, q)),
+                  reinterpret_cast<float4*>(static_cast<char*>(sq.base) + (unsigned long long)row * sq.bytes),
+                  (long)(sq.bytes >> 4), tile, ntile, tid, SnapDense{}, SnapDense{});
+    } else if (q < nf + nr) {
+        const int i = q - nf;
+        // a lock-step target: every item is rotated by its own delta, from its own saved position
+        const int delta = pos_shared ? snap_wrap(snap_wrap(pos_shared[0], L.window) - saved, L.window) : 0;
+        const SnapRing ring = snap_ring(L, i, (unsigned)delta);
+        float4* dst = reinterpret_cast<float4*>(L.rings.s[i].base) + (long)row * L.heads * ring.head_stride;
+        snap_copy(reinterpret_cast<const float4*>(snap + snap_offset(L, q)), dst, (long)L.heads * ring.per_head, tile, ntile, tid,
+                  SnapDense{}, ring);
+    } else if (tile == 0) {
+        const int e16 = (int)(L.embed_bytes >> 4);
+        const float4* pe = reinterpret_cast<const float4*>(snap + SNAP_EMBED);
+        float4* de = reinterpret_cast<float4*>(embed + (unsigned long long)it.slot * L.embed_bytes);
+        for (int j = tid; j < e16; j += SNAP_NT) de[j] = pe[j];
+        if (tid == 0) {
+            cmd[S + row] = was_cmd;
+            if (pos_rows) pos_rows[row] = saved;
+            if (was_active == 0u) {                   // a dead snapshot stays dead, as in k_session_restore
+                cmd[row] = (unsigned)(LH_SESSION_CLOSE | LH_SESSION_RESET);
+                __hip_atomic_store(&fault[it.slot], it.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -1137,5 +1232,59 @@ extern "C" int lh_session_restore(const lh_span_t* flat, int n_flat, const lh_sp
         return LH_ERR_ARG;
     hipLaunchKernelGGL(k_session_restore, dim3(SNAP_TILES, n_flat + n_rings + 1), dim3(SNAP_NT), 0, (hipStream_t)stream, L,
                        (float4*)embed, (const char*)snap, cmd, pos_row, pos_shared, fault, (unsigned)gen, row, S);
+    return check_launch();
+}
+
+// ---- suspend / resume of many listeners (ABI 21) ----------------------------------------------------------------------------
+namespace lh {
+// Tiles per (item, section): SNAP_TILES, what the single kernels use, whatever the number of items.  With 64 items in flight
+// that is some 50 000 workgroups, most of them with less than one 16 KB pass to copy, and it is still the count to keep:
+// measured at S = 64, k = 64 (profiles/suspend_many_cost.txt), 4 to 64 tiles cost the same within the run's scatter — park
+// +619 to +666 us, return +484 to +497 us — and 2 tiles cost 110 to 150 us more.  lh_set_tuning(18, n) sets another count for such
+// A/B runs; 0 = SNAP_TILES.
+static int g_snap_tiles = 0;
+int snap_set_tiles(int v) {
+    if (v < 0 || v > 1024) return LH_ERR_ARG;
+    g_snap_tiles = v;
+    return LH_OK;
+}
+static int snap_tiles() { return g_snap_tiles ? g_snap_tiles : SNAP_TILES; }
+static bool snap_rows_args(unsigned long long snap_stride, const void* pos_rows, const void* pos_shared, const void* items,
+                           int n_items, int S) {
+    return !(snap_stride & 15) && !pos_rows != !pos_shared && items && !((unsigned long long)(size_t)items & 3) && n_items >= 1 &&
+           n_items <= S;
+}
+}  // namespace lh
+
+extern "C" int lh_session_save_rows(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads,
+                                    int ring_rows, int window, const void* embed, int embed_bytes, void* snaps,
+                                    unsigned long long snap_stride, const unsigned* cmd, const unsigned* active,
+                                    const int* pos_rows, const int* pos_shared, const lh_snap_item_t* items, int n_items, int S,
+                                    lh_stream_t stream) {
+    using namespace lh;
+    SnapLayout L;
+    if (!cmd || !active ||
+        !snap_layout(flat, n_flat, rings, n_rings, heads, ring_rows, window, embed, embed_bytes, snaps, snap_stride, 0, S, L) ||
+        !snap_rows_args(snap_stride, pos_rows, pos_shared, items, n_items, S))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_save_rows, dim3(snap_tiles(), n_flat + n_rings + 1, n_items), dim3(SNAP_NT), 0,
+                       (hipStream_t)stream, L, (const char*)embed, (char*)snaps, snap_stride, cmd, active, pos_rows, pos_shared,
+                       items, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_restore_rows(const lh_span_t* flat, int n_flat, const lh_span_t* rings, int n_rings, int heads,
+                                       int ring_rows, int window, void* embed, int embed_bytes, const void* snaps,
+                                       unsigned long long snap_stride, unsigned* cmd, int* pos_rows, const int* pos_shared,
+                                       unsigned* fault, const lh_snap_item_t* items, int n_items, int S, lh_stream_t stream) {
+    using namespace lh;
+    SnapLayout L;
+    if (!cmd || !fault ||
+        !snap_layout(flat, n_flat, rings, n_rings, heads, ring_rows, window, embed, embed_bytes, snaps, snap_stride, 0, S, L) ||
+        !snap_rows_args(snap_stride, pos_rows, pos_shared, items, n_items, S))
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_restore_rows, dim3(snap_tiles(), n_flat + n_rings + 1, n_items), dim3(SNAP_NT), 0,
+                       (hipStream_t)stream, L, (char*)embed, (const char*)snaps, snap_stride, cmd, pos_rows, pos_shared, fault,
+                       items, S);
     return check_launch();
 }

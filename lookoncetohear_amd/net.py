@@ -885,6 +885,17 @@ class Net(_cabi.HipHost, nn.Module):
             lib.call("lh_embed_proj_ln", P(embed), P(pk["emb_w"]), P(pk["emb_b"]), P(pk["emb_ln_w"]), P(pk["emb_ln_b"]),
                      P(gain_raw), P(gain), embed.shape[0], st)
 
+    def _speaker_gain_rows(self, embed: torch.Tensor, gain_raw: torch.Tensor, gain: torch.Tensor, items: torch.Tensor):
+        """`_speaker_gain` for the rows of an item table [k, 4] on the device (lh_snap_item_t): gain[row] from embed[slot],
+        every tensor whole, [S, ...].  The same two kernels whatever k is; a row's bits are those of the per-row call."""
+        lib = self._lib(embed)
+        pk = self._weights(embed.device)
+        st = self._stream(embed.device)
+        P = lambda t: t.data_ptr()
+        with self._device_ctx(embed):
+            lib.call("lh_embed_proj_ln_rows", P(embed), P(pk["emb_w"]), P(pk["emb_b"]), P(pk["emb_ln_w"]), P(pk["emb_ln_b"]),
+                     P(gain_raw), P(gain), P(items), items.shape[0], embed.shape[0], st)
+
     def _stream_chunk(self, x, gain, sin: dict, sout: dict, rings, pos, y, pk: dict, ws: dict, flag=None,
                       keep_nonfinite: int = 0, write_pos=None):
         """One chunk of ONE frame for `Streamer`: the launches of `_separate` with every state tensor read from `sin` and
@@ -1088,6 +1099,26 @@ class _Span(ctypes.Structure):
     _fields_ = [("base", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
 
 
+def _cuda_device(device) -> torch.device:
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _copy_behind(data: torch.Tensor, event, dev: torch.device):
+    """`data` copied into the memory of GPU `dev` behind `event`, without waiting: (the copy, an event behind it)."""
+    if data.is_cuda:                                        # the copy is issued on the source's current stream
+        cur = torch.cuda.current_stream(data.device)
+        if event is not None:
+            cur.wait_event(event)
+        data.record_stream(cur)
+    data = data.to(dev, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    return data, ev
+
+
 class SessionSnapshot:
     """One listener's streaming state as a value: what `SessionStreamer.suspend` takes out and `resume` puts back, into any
     slot of any `SessionStreamer` of the same model — after a minute, on another GPU, in another process.
@@ -1100,6 +1131,7 @@ class SessionSnapshot:
     under the weights it was computed with; nothing checks that.  `to` never waits for the device; `cpu`, `save` and `load`
     may: they are not for the chunk loop."""
     MAGIC, VERSION, HEADER_BYTES = 0x5353484c, 1, 256       # LH_SNAPSHOT_*
+    batch, index = None, 0                                  # a view of a `SessionSnapshotBatch`: the batch and the row
 
     def __init__(self, data: torch.Tensor, layout: tuple, event=None):
         self.data, self.layout, self.event = data, tuple(layout), event
@@ -1119,21 +1151,12 @@ class SessionSnapshot:
         """The snapshot in the memory of `device`: this object if it is there already, else a copy enqueued behind the event.
         From device memory or pinned host memory (what `cpu` and `load` return where a GPU is present) the copy is asynchronous;
         from pageable host memory it is staged and the host may wait for it."""
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _cuda_device(device)
         if dev == self.data.device:
             return self
         if dev.type != "cuda":
             return self.cpu()
-        if self.data.is_cuda:                               # the copy is issued on the source's current stream
-            cur = torch.cuda.current_stream(self.data.device)
-            if self.event is not None:
-                cur.wait_event(self.event)
-            self.data.record_stream(cur)
-        data = self.data.to(dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
+        data, ev = _copy_behind(self.data, self.event, dev)
         return SessionSnapshot(data, self.layout, ev)
 
     def cpu(self) -> "SessionSnapshot":
@@ -1158,6 +1181,15 @@ class SessionSnapshot:
         """A snapshot from `save`'s file, in host memory or on `device`.  ValueError: not a snapshot, another layout version, or
         a size that does not match the header."""
         raw = np.fromfile(path, dtype=np.uint8)
+        layout, total = cls._header(raw, path)
+        if cls.layout_bytes(layout) != raw.size or total != raw.size:
+            raise ValueError(f"{path}: {raw.size} bytes, the header's sizes make {cls.layout_bytes(layout)} (total word {total})")
+        snap = cls(cls._pinned(torch.from_numpy(raw)), layout, None)
+        return snap if device is None else snap.to(device)
+
+    @classmethod
+    def _header(cls, raw: np.ndarray, path: str):
+        """(layout, total bytes) as the header at the start of `raw` states them.  ValueError: not a snapshot's header."""
         if raw.size < cls.HEADER_BYTES + 16:
             raise ValueError(f"{path}: {raw.size} bytes, not a session snapshot")
         head = raw[:cls.HEADER_BYTES].view("<u4").astype(np.int64)
@@ -1166,11 +1198,104 @@ class SessionSnapshot:
         n_flat, n_rings = int(head[3]), int(head[4])
         if n_flat < 1 or n_rings < 1 or 8 + n_flat + n_rings > cls.HEADER_BYTES // 4:
             raise ValueError(f"{path}: header names {n_flat} state tensors and {n_rings} rings")
-        layout = tuple(int(v) for v in head[3:8 + n_flat + n_rings])
-        if cls.layout_bytes(layout) != raw.size or int(head[2]) != raw.size:
-            raise ValueError(f"{path}: {raw.size} bytes, the header's sizes make {cls.layout_bytes(layout)} (total word {int(head[2])})")
-        snap = cls(cls._pinned(torch.from_numpy(raw)), layout, None)
-        return snap if device is None else snap.to(device)
+        return tuple(int(v) for v in head[3:8 + n_flat + n_rings]), int(head[2])
+
+
+class SessionSnapshotBatch:
+    """k listeners' snapshots as ONE value: what `SessionStreamer.suspend_many` / `drain` take out and `resume_many` puts back
+    — a whole streamer moves in one launch and one copy.
+    `data`: ONE uint8 tensor [k, stride]; row i holds snapshot i in its leading `nbytes` = `SessionSnapshot.layout_bytes(layout)`
+    bytes (stride >= nbytes, a multiple of 16; what lies behind is padding nobody writes).  `layout` and `event` as for a
+    `SessionSnapshot`: one layout, and ONE event behind the launch or copy that filled all of `data`.
+    `batch[i]` is a `SessionSnapshot` whose `data` is a view of row i — same memory, same event — so `resume(slot, batch[i])`
+    works, and `resume_many` recognises views of one batch and uses the batch in place.  `to` never waits for the device;
+    `cpu`, `save` and `load` may."""
+
+    def __init__(self, data: torch.Tensor, layout: tuple, event=None):
+        self.data, self.layout, self.event = data, tuple(layout), event
+        self.nbytes = SessionSnapshot.layout_bytes(self.layout)
+        if data.dim() != 2 or data.dtype != torch.uint8 or data.stride(1) != 1 or data.shape[1] < self.nbytes or \
+                data.shape[1] % 16 or (data.shape[0] > 1 and data.stride(0) != data.shape[1]):
+            raise ValueError(f"a batch is a contiguous uint8 [k, stride >= {self.nbytes}, a multiple of 16], got "
+                             f"{tuple(data.shape)} {data.dtype}")
+
+    def __len__(self) -> int:
+        return self.data.shape[0]
+
+    def __getitem__(self, i: int) -> SessionSnapshot:
+        i = range(len(self))[i]                             # negative indexes; IndexError ends an iteration
+        snap = SessionSnapshot(self.data[i, :self.nbytes], self.layout, self.event)
+        snap.batch, snap.index = self, i
+        return snap
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def to(self, device) -> "SessionSnapshotBatch":
+        """The batch in the memory of `device`: this object if it is there already, else ONE copy enqueued behind the event."""
+        dev = _cuda_device(device)
+        if dev == self.data.device:
+            return self
+        if dev.type != "cuda":
+            return self.cpu()
+        data, ev = _copy_behind(self.data, self.event, dev)
+        return SessionSnapshotBatch(data, self.layout, ev)
+
+    def cpu(self) -> "SessionSnapshotBatch":
+        """In host memory.  Waits for the launch that fills the batch."""
+        if not self.data.is_cuda:
+            return self
+        if self.event is not None:
+            self.event.synchronize()
+        return SessionSnapshotBatch(SessionSnapshot._pinned(self.data.cpu()), self.layout, None)
+
+    @classmethod
+    def stack(cls, snapshots, device=None) -> "SessionSnapshotBatch":
+        """A batch of single snapshots of one layout, on `device` (default: where the first one lies).  One copy per snapshot,
+        each ordered behind that snapshot's event on the device's current stream; the host does not wait for device memory."""
+        snaps = list(snapshots)
+        if not snaps:
+            raise ValueError("no snapshots to stack")
+        layout = snaps[0].layout
+        for sn in snaps:
+            if sn.layout != layout or sn.data.numel() != SessionSnapshot.layout_bytes(layout):
+                raise ValueError(f"snapshots of different layouts: {sn.layout} ({sn.data.numel()} bytes) and {layout}")
+        dev = _cuda_device(snaps[0].data.device if device is None else device)
+        if dev.type != "cuda":
+            return cls(SessionSnapshot._pinned(torch.stack([sn.cpu().data for sn in snaps])), layout, None)
+        data = torch.empty(len(snaps), SessionSnapshot.layout_bytes(layout), dtype=torch.uint8, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        for i, sn in enumerate(snaps):
+            sn = sn.to(dev)
+            if sn.event is not None:
+                cur.wait_event(sn.event)
+            sn.data.record_stream(cur)
+            data[i].copy_(sn.data, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        return cls(data, layout, ev)
+
+    def save(self, path: str):
+        """The k snapshots back to back, unpadded, each in `SessionSnapshot.save`'s format: a header's total word says where the
+        next one starts."""
+        self.cpu().data[:, :self.nbytes].contiguous().numpy().tofile(path)
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "SessionSnapshotBatch":
+        """A batch from `save`'s file, in host memory or on `device`.  ValueError: not snapshots back to back, sizes that do not
+        add up, or snapshots of more than one layout."""
+        raw = np.fromfile(path, dtype=np.uint8)
+        layout, total = SessionSnapshot._header(raw, path)
+        n = SessionSnapshot.layout_bytes(layout)
+        if total != n or raw.size % n:
+            raise ValueError(f"{path}: {raw.size} bytes, the first header's sizes make {n} (total word {total})")
+        rows = raw.reshape(-1, n)
+        for i in range(1, rows.shape[0]):
+            if SessionSnapshot._header(rows[i], path) != (layout, total):
+                raise ValueError(f"{path}: snapshot {i} has another layout than snapshot 0")
+        batch = cls(SessionSnapshot._pinned(torch.from_numpy(rows)), layout, None)
+        return batch if device is None else batch.to(device)
 
 
 class SessionStreamer:
@@ -1243,6 +1368,10 @@ class SessionStreamer:
     closed or suspended and resumed between two steps gives its previous listener's row up first, like any listener that left.  A
     listener the device had closed in the chunk before `suspend` (the fault word not yet seen) makes a dead snapshot: resuming
     it leaves the slot idle on the device and lists it in `faults()` after that `step`.  Neither call waits for the device.
+    Many at once: `suspend_many(slots)` / `drain()` / `resume_many(slots, snapshots)` are those calls in order for any number of
+    listeners with a number of launches that does not depend on it — one `lh_session_save_rows` into one `SessionSnapshotBatch`
+    tensor; in `step` one `lh_session_restore_rows` and one `lh_embed_proj_ln_rows` per batch, behind one copy of an item table.
+    `suspend`, `resume` and a streamer that never calls the batched methods enqueue what they always did.
     A snapshot is only meaningful under the weights it was taken with: that is the caller's to keep."""
     RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
     ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
@@ -1308,6 +1437,7 @@ class SessionStreamer:
                              *[sp.bytes for sp in self._spans_rings])
         self._snap_bytes = SessionSnapshot.layout_bytes(self._snap_layout)
         self._resumes = {}                                  # slot -> [snapshot, embedding set since `resume` or None]
+        self._resume_batches = []                           # `resume_many`: (batch, {slot: (index, the slot's entry above)})
         self.pace = bool(pace)
         if pace:
             self._ring = torch.zeros(2, S, dtype=torch.int32, device=dev)    # per row: ring position | the chunk's write slot
@@ -1438,6 +1568,7 @@ class SessionStreamer:
         self._gen = [0] * self.S
         self._pending.clear()
         self._resumes.clear()
+        self._resume_batches.clear()
         if self.enroll_chunks:
             self._ewords.zero_()
             self._edone.zero_()
@@ -1610,15 +1741,14 @@ class SessionStreamer:
         self._resumes.pop(slot, None)                       # resumed and closed before a `step`: nothing is restored
         self._pending[slot] = self.RESET | self.CLOSE
 
-    def _snap_args(self, k: int, slot: int):
-        """The leading arguments of lh_session_save / lh_session_restore up to the embedding: ping-pong set k, `slot`."""
+    def _snap_args(self, k: int, slot=None):
+        """The leading arguments of lh_session_save / lh_session_restore up to the embedding: ping-pong set k, `slot`; of the
+        *_rows forms without a slot: the embeddings of all slots."""
         live, rings, emb = self._spans_live[k], self._spans_rings, self._st.embed
         return (ctypes.addressof(live), len(live), ctypes.addressof(rings), len(rings), *self._ring_geom,
-                emb[slot].data_ptr(), emb.shape[1] * emb.element_size())
+                (emb if slot is None else emb[slot]).data_ptr(), emb.shape[1] * emb.element_size())
 
-    def suspend(self, slot: int) -> SessionSnapshot:
-        """The listener of open `slot` as a `SessionSnapshot`: their state as of the last `step`.  From the next `step` on the
-        slot is idle exactly as after `close(slot)`.  Enqueues one launch and returns; never waits for the device."""
+    def _suspendable(self, slot: int):
         self._slot(slot)
         if slot in self._capturing or slot in self._embedding:
             raise ValueError(f"slot {slot} is enrolling: it has no session yet")
@@ -1626,6 +1756,11 @@ class SessionStreamer:
             raise ValueError(f"slot {slot} is not open")
         if slot in self._pending:
             raise ValueError(f"slot {slot} was opened or resumed and no step has served it yet: it has no state on the device")
+
+    def suspend(self, slot: int) -> SessionSnapshot:
+        """The listener of open `slot` as a `SessionSnapshot`: their state as of the last `step`.  From the next `step` on the
+        slot is idle exactly as after `close(slot)`.  Enqueues one launch and returns; never waits for the device."""
+        self._suspendable(slot)
         st, net, S = self._st, self.net, self.S
         row = self._row_of[slot] if self.compact else slot
         words = self._tables[3:] if self.compact else self._words       # cmd from the host | cmd from the device | active
@@ -1641,10 +1776,49 @@ class SessionStreamer:
         self._pending[slot] = self.RESET | self.CLOSE
         return SessionSnapshot(data, self._snap_layout, event)
 
-    def resume(self, slot: int, snapshot: SessionSnapshot):
-        """From the next `step` on idle `slot` is the listener of `snapshot`: carried state, ring history, ring position and
-        speaker embedding are theirs (there is no embedding argument).  ValueError for a snapshot of another model layout.
-        Never waits for the device: a snapshot in another GPU's memory is copied over behind its event."""
+    def _items(self, items: list) -> torch.Tensor:
+        """A table of lh_snap_item_t (row, slot, generation, index) on the device: a FRESH pinned array and one asynchronous
+        copy, as the command words travel."""
+        src = self.net._host_words(4 * len(items), self.device)
+        src.numpy().reshape(-1, 4)[:] = items
+        table = torch.empty(len(items), 4, dtype=torch.int32, device=self.device)
+        table.copy_(src.view(-1, 4), non_blocking=True)
+        return table
+
+    def suspend_many(self, slots) -> "SessionSnapshotBatch":
+        """`suspend(s)` for every s of `slots`, in order, between the same two steps — the same snapshot bytes, the same slots idle
+        afterwards — as ONE launch (`lh_session_save_rows`) into one fresh [k, snapshot bytes] tensor, behind one asynchronous
+        copy of the item table.  Every ValueError of `suspend` applies, a slot named twice is one more; everything is checked
+        before anything is enqueued or changed.  Never waits for the device."""
+        slots = [int(s) for s in slots]
+        for slot in slots:
+            self._suspendable(slot)
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"a slot is named twice: {slots}")
+        st, net, S, k = self._st, self.net, self.S, len(slots)
+        data = torch.empty(k, self._snap_bytes, dtype=torch.uint8, device=self.device)
+        event = None
+        if k:
+            words = self._tables[3:] if self.compact else self._words   # cmd from the host | cmd from the device | active
+            pos_rows, pos_shared = (self._ring[0].data_ptr(), None) if self.pace else (None, st.pos.data_ptr())
+            items = self._items([(self._row_of[s] if self.compact else s, s, 0, i) for i, s in enumerate(slots)])
+            with torch.no_grad(), net._device_ctx(st.chunk):
+                net._lib(st.chunk).call("lh_session_save_rows", *self._snap_args(st.parity), data.data_ptr(), data.stride(0),
+                                        words.data_ptr(), words[2].data_ptr(), pos_rows, pos_shared, items.data_ptr(), k, S,
+                                        net._stream(self.device))
+                event = net._record_event(self.device)
+        for slot in slots:
+            self._gen[slot] = 0
+            self._enrolled.pop(slot, None)
+            self._pending[slot] = self.RESET | self.CLOSE
+        return SessionSnapshotBatch(data, self._snap_layout, event)
+
+    def drain(self):
+        """Everyone leaves: (the active slots in ascending order, `suspend_many` of them)."""
+        slots = self.active
+        return slots, self.suspend_many(slots)
+
+    def _resumable(self, slot: int, layout: tuple, nbytes: int):
         self._slot(slot)
         if slot in self.active:
             raise ValueError(f"slot {slot} is open: close() it first")
@@ -1652,16 +1826,53 @@ class SessionStreamer:
             self.poll()                                     # an aborted capture has left the slot idle
             if slot in self._capturing or slot in self._embedding:
                 raise ValueError(f"slot {slot} is enrolling: close() it first")
-        if snapshot.layout != self._snap_layout or snapshot.data.numel() != self._snap_bytes:
-            raise ValueError(f"the snapshot's layout {snapshot.layout} ({snapshot.data.numel()} bytes) is not this Net's "
+        if layout != self._snap_layout or nbytes != self._snap_bytes:
+            raise ValueError(f"the snapshot's layout {layout} ({nbytes} bytes) is not this Net's "
                              f"{self._snap_layout} ({self._snap_bytes} bytes)")
+
+    def _resumed(self, slot: int, snapshot: SessionSnapshot) -> list:
         self._enroll_faults.discard(slot)
         self._enrolled.pop(slot, None)
         gen = self._new_gen()
         self._gen[slot] = gen
         # no RESET: lh_session_restore writes every byte a RESET would zero, apart from what the chunk rewrites itself
         self._pending[slot] = self.OPEN | (gen << self.GEN_SHIFT)
-        self._resumes[slot] = [snapshot.to(self.device), None]
+        self._resumes[slot] = entry = [snapshot, None]
+        return entry
+
+    def resume(self, slot: int, snapshot: SessionSnapshot):
+        """From the next `step` on idle `slot` is the listener of `snapshot`: carried state, ring history, ring position and
+        speaker embedding are theirs (there is no embedding argument).  ValueError for a snapshot of another model layout.
+        Never waits for the device: a snapshot in another GPU's memory is copied over behind its event."""
+        self._resumable(slot, snapshot.layout, snapshot.data.numel())
+        self._resumed(slot, snapshot.to(self.device))
+
+    def resume_many(self, slots, snapshots):
+        """`resume(slots[i], snapshots[i])` for every i, in order — the generations handed out, `set_embedding` and `close`
+        afterwards, dead snapshots, a compacting streamer's holes: all as there — but `step` restores them in ONE launch
+        (`lh_session_restore_rows`) and computes their gains in one call.  `snapshots`: a `SessionSnapshotBatch`, or a sequence
+        of `SessionSnapshot`; views of one batch use that batch in place (any subset, any order), anything else is stacked
+        first.  A batch in another GPU's memory comes over in one copy behind its event.  Everything is checked before anything
+        changes: a slot named twice, an open or enrolling slot and another model's layout are ValueErrors.  Never waits."""
+        slots = [int(s) for s in slots]
+        if isinstance(snapshots, SessionSnapshotBatch):
+            batch, index = snapshots, list(range(len(snapshots)))
+            layouts = [(batch.layout, batch.nbytes)] * len(index)
+        else:
+            snaps = list(snapshots)
+            batch = snaps[0].batch if snaps and all(sn.batch is snaps[0].batch for sn in snaps) else None
+            index = [sn.index for sn in snaps] if batch is not None else list(range(len(snaps)))
+            layouts = [(sn.layout, sn.data.numel()) for sn in snaps]
+        if len(slots) != len(index):
+            raise ValueError(f"{len(slots)} slots for {len(index)} snapshots")
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"a slot is named twice: {slots}")
+        for slot, (layout, nbytes) in zip(slots, layouts):
+            self._resumable(slot, layout, nbytes)
+        if not slots:
+            return
+        batch = SessionSnapshotBatch.stack(snaps, self.device) if batch is None else batch.to(self.device)
+        self._resume_batches.append((batch, {slot: (i, self._resumed(slot, batch[i])) for slot, i in zip(slots, index)}))
 
     def _restore(self):
         """The resumes of this step, behind the copy of the command words (a dead snapshot takes its OPEN back) and ahead of
@@ -1670,7 +1881,13 @@ class SessionStreamer:
         words = self._tables[3:] if self.compact else self._words
         with torch.no_grad(), net._device_ctx(st.chunk):
             lib, stream = net._lib(st.chunk), net._stream(self.device)
+            # `resume_many`: the slots of a batch that still hold that resume (not closed, or closed and resumed again, since)
+            groups = [(batch, [(slot, i) for slot, (i, entry) in group.items() if self._resumes.get(slot) is entry])
+                      for batch, group in self._resume_batches]
+            batched = {slot for _, live in groups for slot, _ in live}
             for slot, (snap, embed) in self._resumes.items():
+                if slot in batched:
+                    continue
                 row = self._row_of[slot] if self.compact else slot
                 net._wait_event(self.device, snap.event, snap.data)
                 pos_row, pos_shared = (self._ring[0, row:row + 1].data_ptr(), None) if self.pace else (None, st.pos.data_ptr())
@@ -1680,7 +1897,22 @@ class SessionStreamer:
                 if embed is not None:                       # `set_embedding` after `resume`
                     st.embed[slot].copy_(embed.reshape(-1), non_blocking=True)
                 self._row_gain(slot, row)
+            for batch, live in groups:                      # one table, one restore launch, one gain call per batch
+                if not live:
+                    continue
+                net._wait_event(self.device, batch.event, batch.data)
+                items = self._items([(self._row_of[slot] if self.compact else slot, slot, self._gen[slot], i)
+                                     for slot, i in live])
+                pos_rows, pos_shared = (self._ring[0].data_ptr(), None) if self.pace else (None, st.pos.data_ptr())
+                lib.call("lh_session_restore_rows", *self._snap_args(st.parity), batch.data.data_ptr(), batch.data.stride(0),
+                         words.data_ptr(), pos_rows, pos_shared, self._fault.data_ptr(), items.data_ptr(), len(live), S, stream)
+                for slot, _ in live:
+                    embed = self._resumes[slot][1]
+                    if embed is not None:                   # `set_embedding` after `resume_many`
+                        st.embed[slot].copy_(embed.reshape(-1), non_blocking=True)
+                net._speaker_gain_rows(st.embed, st.gain_raw, st.gain, items)
         self._resumes.clear()
+        self._resume_batches.clear()
 
     def set_embedding(self, slot: int, embed: torch.Tensor):
         """Re-target an open slot ("look once" at another speaker): the carried state is kept."""

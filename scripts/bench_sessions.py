@@ -27,6 +27,12 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         a paced streamer with every slot open: a step that suspends one listener and, three steps later, a step that resumes
         them, against the steady steps of the same streamer in the same interleaved run; at the largest batch also the park
         and return of 8 listeners at once.  `scatter` is the spread of the steady blocks' p50.
+    python scripts/bench_sessions.py --suspend-many [--slots 64] [--many 1,8,64] [--tiles 4,8,16,32] [--out profiles/xyz.txt]
+        what the batched calls buy, in DEVICE time per chunk as above, in a paced streamer with every slot open.  Per k, one
+        interleaved run of cycles: steady steps, a step that parks k listeners through `suspend_many`, 3 steps, a step that
+        returns them through `resume_many`, steady steps, and the same two steps through the loops of `suspend` / `resume`.
+        The batched step has to be cheaper than the loop by more than three times the scatter of the steady blocks.  --tiles:
+        also the batched steps at the largest k under each tile count per (item, section) (lh_set_tuning key 18).
 """
 import argparse
 import json
@@ -346,12 +352,97 @@ def suspend_bench(net, args):
             f.write(text + "\n")
 
 
+def suspend_many_bench(net, args):
+    from lookoncetohear_amd import _cabi
+
+    def timed_step(ss, chunk, action=None):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if action is not None:
+            action()
+        ss.step(chunk)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    B = args.slots
+    lines = [f"suspend_many / resume_many against the loops of suspend / resume, device time per chunk (HIP events around the calls "
+             f"and the replay), paced streamer, S = {B}, every slot open, {args.move_reps} cycles of: 12 steady steps, a step that "
+             f"parks k, 3 steps, a step that returns k — batched, then the same one by one"]
+    d = synth.batch(list(range(B)), 80000)
+    mix = torch.nn.functional.pad(d["mixture"], (0, 64)).to(DEV)
+    emb = d["embedding_gt"][:, 0].to(DEV)
+    chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+    ss = net.make_session_streamer(B, DEV, pace=True)
+    for s in range(B):
+        ss.open(s, emb[s])
+    dev_steps(ss, chunks, 0, args.warmup)
+    held = []
+    ways = {"suspend_many": lambda k: held.append(ss.suspend_many(range(k))),
+            "resume_many": lambda k: ss.resume_many(range(k), held.pop()),
+            "suspend loop": lambda k: held.append([ss.suspend(s) for s in range(k)]),
+            "resume loop": lambda k: [ss.resume(s, snap) for s, snap in enumerate(held.pop())]}
+
+    def cycles(k, pairs, reps):
+        """-> (steady steps, p50 of each steady block, {way: ms of its steps})"""
+        steady, p50s, ms, i = [], [], {w: [] for pair in pairs for w in pair}, 0
+        for rep in range(reps):
+            for park, back in pairs:
+                blk = [timed_step(ss, chunks[(i + j) % 625]) for j in range(12)][4:]
+                steady += blk
+                p50s.append(pct(blk, 0.5))
+                ms[park].append(timed_step(ss, chunks[(i + 12) % 625], lambda: ways[park](k)))
+                for j in range(3):
+                    timed_step(ss, chunks[(i + 13 + j) % 625])
+                ms[back].append(timed_step(ss, chunks[(i + 16) % 625], lambda: ways[back](k)))
+                i += 17
+        torch.cuda.synchronize()
+        assert ss.faults() == [] and len(ss.active) == B and not held
+        return steady, p50s, ms
+
+    ks = [int(k) for k in args.many.split(",")]
+    for k in ks:
+        steady, p50s, ms = cycles(k, (("suspend_many", "resume_many"), ("suspend loop", "resume loop")), args.move_reps)
+        rs, scatter = stats(steady), max(p50s) - min(p50s)
+        r = {w: stats(v) for w, v in ms.items()}
+        for w in ms:
+            lines.append(f"S={B:3d} k={k:2d} {w:13s} ({r[w]['n']} times, {k * ss._snap_bytes / 1e6:.1f} MB): p50 {r[w]['p50_ms']:.4f} "
+                         f"max {r[w]['max_ms']:.4f} ms   steady steps: p50 {rs['p50_ms']:.4f} p99 {rs['p99_ms']:.4f} ms   "
+                         f"p50 cost {1e3 * (r[w]['p50_ms'] - rs['p50_ms']):+.1f} us, scatter of the steady blocks {1e3 * scatter:.1f} us")
+        for many, loop in (("suspend_many", "suspend loop"), ("resume_many", "resume loop")):
+            gain = r[loop]["p50_ms"] - r[many]["p50_ms"]
+            lines.append(f"S={B:3d} k={k:2d} {many} is {1e3 * gain:+.1f} us cheaper than the loop (p50): "
+                         f"{'MORE than' if gain > 3 * scatter else 'NOT more than'} three times the scatter ({1e3 * scatter:.1f} us)")
+        if k == B:
+            lines.append(f"S={B:3d} k={k:2d} the step that returns everyone, chunk included: p50 {r['resume_many']['p50_ms']:.4f} max "
+                         f"{r['resume_many']['max_ms']:.4f} ms batched, p50 {r['resume loop']['p50_ms']:.4f} max "
+                         f"{r['resume loop']['max_ms']:.4f} ms one by one, against the 8 ms chunk period")
+    if args.tiles:
+        lib, k = _cabi.load(), max(ks)
+        for t in [int(t) for t in args.tiles.split(",")]:
+            lib.call("lh_set_tuning", 18, t)
+            steady, p50s, ms = cycles(k, (("suspend_many", "resume_many"),), max(4, args.move_reps // 2))
+            rs = stats(steady)
+            lines.append(f"S={B:3d} k={k:2d} {t:3d} tiles per (item, section): " + "   ".join(
+                f"{w} p50 {stats(v)['p50_ms']:.4f} max {max(v):.4f} ms (cost {1e3 * (stats(v)['p50_ms'] - rs['p50_ms']):+.1f} us)"
+                for w, v in ms.items()) + f"   scatter {1e3 * (max(p50s) - min(p50s)):.1f} us")
+        lib.call("lh_set_tuning", 18, 0)
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--enroll", action="store_true")
     ap.add_argument("--pace", action="store_true")
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--suspend", action="store_true")
+    ap.add_argument("--suspend-many", action="store_true")
+    ap.add_argument("--many", default="1,8,64")
+    ap.add_argument("--tiles", default="")
     ap.add_argument("--slots", type=int, default=64)
     ap.add_argument("--open", default="1,4,16,64")
     ap.add_argument("--move-reps", type=int, default=20)
@@ -374,6 +465,8 @@ def main():
         return pace_bench(net, args)
     if args.suspend:
         return suspend_bench(net, args)
+    if args.suspend_many:
+        return suspend_many_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
