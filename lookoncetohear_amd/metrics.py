@@ -11,6 +11,10 @@ import torch.nn.functional as F
 
 
 def si_snr(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Zero-mean SI-SDR over the last axis, in `pred`'s dtype.  As in torchmetrics, eps follows that dtype: 1.19e-7 on
+    float32 inputs — the value the reference's eval and lh_metric_sums use — but 2.2e-16 on float64 ones.  The two differ
+    wherever eps decides the result (a silent or constant signal), so this function on doubles is NOT the float64 statement
+    of the fp32 metric; tests/data_stage_cases.py restates that with eps fixed at the fp32 value."""
     eps = torch.finfo(pred.dtype).eps
     pred = pred - pred.mean(-1, keepdim=True)
     target = target - target.mean(-1, keepdim=True)

@@ -29,7 +29,8 @@ def convolve_trunc(src: np.ndarray, rir2: np.ndarray, exact: bool = False) -> np
 
 
 def mix(events, noise, noise_scale: float, tgt_idx: int):
-    """events: list of float32 tensors [2, N]; noise [2, N].  MixLibriSpeechNoisyEnrollNorm.py:176-202 (eval path)."""
+    """events: list of float32 tensors [2, N]; noise [2, N].  MixLibriSpeechNoisyEnrollNorm.py:176-202 (eval path).
+    `tgt_idx` counts through `events + [noise]`: the reference only ever picks an event, the C ABI also allows the noise row."""
     events = [e.clone().float() for e in events]
     noise = noise.clone().float() * noise_scale
     norm_factor = torch.abs(sum(events) + noise).max()
@@ -38,7 +39,7 @@ def mix(events, noise, noise_scale: float, tgt_idx: int):
             events[i] /= norm_factor
         noise /= norm_factor
     mixture = sum(events) + noise
-    return mixture, events[tgt_idx], norm_factor
+    return mixture, (events + [noise])[tgt_idx], norm_factor
 
 
 def render(srcs: np.ndarray, rirs: np.ndarray, noise_scale: float, tgt_idx: int, exact: bool = False):

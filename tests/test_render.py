@@ -60,7 +60,7 @@ def test_emulated_kernels_match_oracle():
     nf = _check(rr, "cpu", [2], 4500, 3000, loud=4.0, reverb=True)   # room-length response: overlap-save FFT path, peak > 1
     assert float(nf.min()) > 1.0
     _check(rr, "cpu", [4], 9000, 1024)                          # shortest FFT-path response, three output blocks
-    _check(rr, "cpu", [5], 2100, 1000)                          # one tap short of it: direct form, several tap stages
+    _check(rr, "cpu", [5], 2100, 1000)                          # below it: direct form, ONE tap stage (FIR_KT = 2048)
     _check(rr, "cpu", [3], 300, 7)                              # shorter than a tile, tiny filter
     with pytest.raises(ValueError):
         rr.render(torch.zeros(1, 4, 100), torch.zeros(1, 3, 2, 8), torch.ones(1, 4), torch.zeros(1, dtype=torch.int64))
