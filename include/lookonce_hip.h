@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (21); bumped on any signature change. */
+/* ABI version of this header (22); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -716,6 +716,49 @@ int lh_session_restore_rows(const lh_span_t* flat, int n_flat, const lh_span_t* 
                             int n_items, int S, lh_stream_t stream);
 int lh_embed_proj_ln_rows(const float* embed, const float* w, const float* bias, const float* ln_w, const float* ln_b,
                           float* scratch, float* gain, const lh_snap_item_t* items, int n_items, int S, lh_stream_t stream);
+
+/* Packets (ABI 22): the transport side of a paced host.  Clients send contiguous PCM in packets of any size, fp32 or 16-bit;
+ * the device keeps a small input FIFO per slot, cuts its own [2][192] windows (128 new samples + 64 look-ahead) into chunk_in
+ * and decides by itself which slots are present — the host copies neither windows nor hold words.  Everything behind chunk_in
+ * and hold is the paced family above, unchanged.
+ *   fifo       [S][2][R] fp32, 16-byte aligned: a ring per slot and channel.  R a power of two, 256 <= R <= 2^24.
+ *   wr, rd     [S] each, 32-bit SAMPLE COUNTERS that wrap modulo 2^32 (at 16 kHz: after 74 hours), zero at start.  R divides
+ *              2^32, so sample c lives at ring index c & (R - 1) and the fill is the unsigned difference wr[s] - rd[s], both
+ *              across the wrap.  rd only ever moves by 128 from 0: every window starts on a multiple of 128 samples and meets
+ *              the ring's end only at a multiple of 64, so windows move 16 bytes at a time.
+ *   staging    device buffer with the samples of one tick's packets, 4-byte aligned, staging_bytes long; `format` says what an
+ *              element is: LH_FEED_F32 (4 bytes, copied as bit patterns) or LH_FEED_S16 (2 bytes, value * 2^-15: exact).
+ *   items      table of n_items >= 1 entries in DEVICE memory (4-byte aligned).  Item i is one packet of items[i].n samples for
+ *              slot items[i].slot, planar in staging: channel 0 at elements [offset, offset + n), channel 1 at
+ *              [offset + n, offset + 2 n).  `at` is the slot's write counter before the packet — the HOST's mirror of wr[slot].
+ *              flags: LH_FEED_FLUSH drops the slot's buffered input first: rd[slot] = 0 and `at` is taken as 0; n = 0 is legal.
+ *              The host hands out at most one item per slot per call, and never more than R - (wr - rd) samples: the entry
+ *              points cannot know that, a ring that is overrun loses its oldest samples.
+ * Who writes which word:
+ *   lh_session_feed   (an eager launch between two chunks, like lh_session_restore_rows; grid over tile x item) stores sample i
+ *              of an item to fifo[slot][ch][(at + i) & (R - 1)] and, one thread per item, wr[slot] = at + n (FLUSH: and
+ *              rd[slot] = 0).  No thread READS wr, so the workgroups of an item have nothing to race on.  Skipped whole, by every
+ *              workgroup and before any address is formed: an item whose slot is outside [0, S), whose n is negative or larger
+ *              than R, or whose samples would reach outside [0, staging_bytes).
+ *   lh_session_frame  (the FIRST node of the chunk's graph; one wave per slot, the only writer of hold[s] and the only other
+ *              writer of rd[s]; it reads both counters before it writes either word)  avail = wr[s] - rd[s].  avail >= 192:
+ *              samples [rd, rd + 192) of both channels go to chunk_in[s], hold[s] = 0, rd[s] += 128.  Otherwise hold[s] = 1 and
+ *              chunk_in[s] is not touched — no paced kernel looks at a held row's input.  It does not ask what the slot is:
+ *              open, capturing and idle slots are framed alike, as the lock-step forms gate an idle slot's row.
+ *   lh_session_emit_s16  (a node after lh_session_end[_rows]_paced, in a host that answers in 16-bit PCM)  out [S][2][128] fp32 ->
+ *              out16 [S][2][128] int16, both 16-byte aligned:  y = clamp(rint(32768 x), -32768, 32767), round half even,
+ *              saturating, NaN -> 0 (the end kernel has zeroed every faulted or held row, so none arrives from a session).
+ * The feed launch and the chunk's graph are ordered by the stream, and the host mirrors both counters with the same arithmetic:
+ * it knows what every launch will find, the device follows, and no word is ever read back.
+ * LH_ERR_ARG: null or misaligned pointer, wr == rd, S <= 0, R not a power of two in [256, 2^24], n_items outside [1, 65535],
+ * an unknown format, out == out16.  None of the three allocates, synchronises or reads device memory on the host. */
+enum { LH_FEED_F32 = 0, LH_FEED_S16 = 1, LH_FEED_FLUSH = 1 };
+typedef struct { int slot; int offset; int n; unsigned at; unsigned flags; } lh_feed_item_t;   /* 20 bytes */
+int lh_session_feed(const void* staging, unsigned long long staging_bytes, int format, const lh_feed_item_t* items, int n_items,
+                    float* fifo, unsigned* wr, unsigned* rd, int R, int S, lh_stream_t stream);
+int lh_session_frame(const float* fifo, const unsigned* wr, unsigned* rd, float* chunk_in, unsigned* hold, int R, int S,
+                     lh_stream_t stream);
+int lh_session_emit_s16(const float* out, short* out16, int S, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -58,6 +58,11 @@ SIGNATURES = {
     "lh_session_save_rows": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, c_ulonglong, _P, _P, _P, _P, _P, _I, _I, _P],
     "lh_session_restore_rows": [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, c_ulonglong, _P, _P, _P, _P, _P, _I, _I, _P],
     "lh_embed_proj_ln_rows": [_P] * 8 + [_I, _I, _P],
+    # packets (ABI 22): per-slot input FIFOs fed with the clients' packets, windows and hold words made on the device,
+    # 16-bit output; SessionStreamer(pace=True, packets=True)
+    "lh_session_feed": [_P, c_ulonglong, _I, _P, _I, _P, _P, _P, _I, _I, _P],
+    "lh_session_frame": [_P] * 5 + [_I, _I, _P],
+    "lh_session_emit_s16": [_P, _P, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)

@@ -978,6 +978,103 @@ __global__ void __launch_bounds__(SNAP_NT) k_session_restore_rows(SnapLayout L, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Packets (ABI 22): the clients' PCM goes in as it arrives and the device cuts its own windows.  Per slot and channel a ring
+// fifo[S][2][R] of fp32 samples, R a power of two, and two 32-bit sample counters that wrap modulo 2^32: wr[s] samples written,
+// rd[s] samples consumed.  R divides 2^32, so the ring index is `counter & (R - 1)` and the fill is the unsigned difference
+// wr - rd, both across the wrap.  Who writes what:
+//   k_session_feed   (eager, between two chunks) writes the samples of its items and wr[slot] = at + n, where `at` is the HOST's
+//                    mirror of the counter: no thread reads wr, so the workgroups of an item have nothing to race on.  An item
+//                    with FLUSH also writes rd[slot] = 0 (and takes `at` as 0): the slot's buffered input is dropped.
+//   k_session_frame  (first node of the chunk's graph, one wave per slot) is the only other writer of rd[s] and the only writer
+//                    of hold[s]; it reads both counters before it writes either word.
+// The two never run at once (one stream), and the host mirrors both counters with the same arithmetic: it knows what every
+// launch will find, so the device follows and nothing is ever read back.
+// rd only moves by 128 from 0: a window starts on a multiple of 128 samples, R is a multiple of 256, so every float4 of a
+// window lies inside the ring and the frame kernel moves 16 bytes at a time — bytes, not numbers.
+// ------------------------------------------------------------------------------------------------------
+constexpr int SF_NT = 256, SF_MAX_TILES = 16;
+struct FeedItem { int slot, n; long off; unsigned at, flags; bool ok; };
+// An item is served or skipped WHOLE, and every workgroup of it decides alike from the same five words, before an address
+// is formed: slot in [0, S), 0 <= n <= R, and both channels [off, off + 2 n) inside the staging buffer of `elems` elements.
+__device__ __forceinline__ FeedItem feed_item(const lh_feed_item_t* __restrict__ items, int i, int S, int R,
+                                              unsigned long long elems) {
+    const lh_feed_item_t it = items[i];
+    FeedItem f{it.slot, it.n, (long)it.offset, it.at, it.flags, false};
+    f.ok = (unsigned)it.slot < (unsigned)S && it.n >= 0 && it.n <= R && it.offset >= 0 &&
+           (unsigned long long)it.offset + 2ull * (unsigned long long)it.n <= elems;
+    if (f.flags & LH_FEED_FLUSH) f.at = 0u;
+    return f;
+}
+
+// grid (tiles, n_items), block 256.  T = unsigned (fp32 samples, copied as bit patterns) or short (s16, scaled by 2^-15: exact)
+template <class T>
+__global__ void __launch_bounds__(SF_NT) k_session_feed(const T* __restrict__ staging, unsigned long long elems,
+                                                        const lh_feed_item_t* __restrict__ items, unsigned* __restrict__ fifo,
+                                                        unsigned* wr, unsigned* rd, int R, int S) {
+    const int tid = threadIdx.x, tile = blockIdx.x, ntile = gridDim.x;
+    const FeedItem f = feed_item(items, blockIdx.y, S, R, elems);
+    if (!f.ok) return;
+    const unsigned mask = (unsigned)R - 1u;
+    const T* src = staging + f.off;                            // planar: channel 0 [0, n), channel 1 [n, 2 n)
+    unsigned* ring = fifo + (long)f.slot * NMIC * R;
+    for (int e = tile * SF_NT + tid; e < NMIC * f.n; e += ntile * SF_NT) {
+        const int ch = e >= f.n ? 1 : 0, i = e - ch * f.n;
+        unsigned bits;
+        if constexpr (sizeof(T) == 2) bits = __float_as_uint((float)src[e] * (1.0f / 32768.0f));
+        else bits = src[e];
+        ring[(long)ch * R + ((f.at + (unsigned)i) & mask)] = bits;
+    }
+    if (tile == 0 && tid == 0) {
+        wr[f.slot] = f.at + (unsigned)f.n;
+        if (f.flags & LH_FEED_FLUSH) rd[f.slot] = 0u;
+    }
+}
+
+// grid S, block 64: one wave per slot.  Pure latency like k_session_capture: the two counters and the lane's float4s of the
+// window are requested together (the masked ring index is inside the ring whatever the counters hold) and only then looked at.
+constexpr int PK_WIN4 = NFFT / 4;              // 48 float4 per channel of a window
+static_assert(NMIC * PK_WIN4 == SS_IN4 && HOP % 4 == 0, "the window is the input row of the session kernels");
+__global__ void __launch_bounds__(SC_NT) k_session_frame(const float* __restrict__ fifo, const unsigned* __restrict__ wr,
+                                                         unsigned* rd, float* __restrict__ chunk_in, unsigned* hold, int R, int S) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    // every lane has loaded both counters before any lane goes on: lane 0, the writer below, cannot overtake a reader
+    const unsigned w = __shfl(wr[s], 0), r = __shfl(rd[s], 0), mask = (unsigned)R - 1u;
+    const int j0 = lane, j1 = 64 + (lane & (SS_IN4 - 64 - 1));          // float4 of the [2][192] row; lanes >= 32 repeat j1
+    const float4* ring = reinterpret_cast<const float4*>(fifo + (long)s * NMIC * R);
+    const int R4 = R >> 2;
+    const float4 v0 = ring[(j0 / PK_WIN4) * R4 + (int)(((r + 4u * (unsigned)(j0 % PK_WIN4)) & mask) >> 2)];
+    const float4 v1 = ring[(j1 / PK_WIN4) * R4 + (int)(((r + 4u * (unsigned)(j1 % PK_WIN4)) & mask) >> 2)];
+    const bool takes = w - r >= (unsigned)NFFT;                         // wave-uniform
+    if (takes) {
+        float4* row = reinterpret_cast<float4*>(chunk_in + (long)s * NMIC * NFFT);
+        row[j0] = v0;
+        if (lane < SS_IN4 - 64) row[j1] = v1;
+    }
+    if (lane == 0) {
+        if (takes) rd[s] = r + (unsigned)HOP;
+        hold[s] = takes ? 0u : 1u;
+    }
+}
+
+// grid over 8 samples per thread, block 256: out [S][2][128] fp32 -> out16 [S][2][128] int16, one 16-byte store per thread
+__device__ __forceinline__ unsigned emit_s16(float x) {
+    float y = rintf(x * 32768.0f);                             // round half even; the scaling by 2^15 is exact
+    y = x != x ? 0.f : fminf(fmaxf(y, -32768.0f), 32767.0f);   // NaN -> 0, +-inf saturate
+    return (unsigned)(int)y & 0xffffu;
+}
+__global__ void __launch_bounds__(SS_NT) k_session_emit_s16(const float4* __restrict__ out, int4* __restrict__ out16, int n8) {
+    const int i = blockIdx.x * SS_NT + threadIdx.x;
+    if (i >= n8) return;
+    const float4 a = out[2 * i], b = out[2 * i + 1];
+    int4 p;
+    p.x = (int)(emit_s16(a.x) | (emit_s16(a.y) << 16));
+    p.y = (int)(emit_s16(a.z) | (emit_s16(a.w) << 16));
+    p.z = (int)(emit_s16(b.x) | (emit_s16(b.y) << 16));
+    p.w = (int)(emit_s16(b.z) | (emit_s16(b.w) << 16));
+    out16[i] = p;
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -1286,5 +1383,48 @@ extern "C" int lh_session_restore_rows(const lh_span_t* flat, int n_flat, const 
     hipLaunchKernelGGL(k_session_restore_rows, dim3(snap_tiles(), n_flat + n_rings + 1, n_items), dim3(SNAP_NT), 0,
                        (hipStream_t)stream, L, (char*)embed, (const char*)snaps, snap_stride, cmd, pos_rows, pos_shared, fault,
                        items, S);
+    return check_launch();
+}
+
+// ---- packets (ABI 22) ---------------------------------------------------------------------------------------------------------
+namespace lh {
+static bool aligned_to(const void* p, unsigned a) { return p && !((unsigned long long)(size_t)p & (a - 1u)); }
+static bool fifo_args(const void* fifo, const void* wr, const void* rd, int R, int S) {
+    return aligned16(fifo) && aligned_to(wr, 4) && aligned_to(rd, 4) && wr != rd && S > 0 && R >= 256 && R <= (1 << 24) &&
+           !(R & (R - 1));
+}
+}  // namespace lh
+
+extern "C" int lh_session_feed(const void* staging, unsigned long long staging_bytes, int format, const lh_feed_item_t* items,
+                               int n_items, float* fifo, unsigned* wr, unsigned* rd, int R, int S, lh_stream_t stream) {
+    using namespace lh;
+    if ((format != LH_FEED_F32 && format != LH_FEED_S16) || !aligned_to(staging, 4) || !aligned_to(items, 4) || n_items < 1 ||
+        n_items > 65535 || !fifo_args(fifo, wr, rd, R, S))
+        return LH_ERR_ARG;
+    // a packet is a few hundred samples: tiles enough for an item that fills the ring, a handful of early-out workgroups else
+    const int want = NMIC * R / (4 * SF_NT), tiles = want < 1 ? 1 : (want > SF_MAX_TILES ? SF_MAX_TILES : want);
+    if (format == LH_FEED_S16)
+        hipLaunchKernelGGL(k_session_feed<short>, dim3(tiles, n_items), dim3(SF_NT), 0, (hipStream_t)stream,
+                           (const short*)staging, staging_bytes / 2, items, (unsigned*)fifo, wr, rd, R, S);
+    else
+        hipLaunchKernelGGL(k_session_feed<unsigned>, dim3(tiles, n_items), dim3(SF_NT), 0, (hipStream_t)stream,
+                           (const unsigned*)staging, staging_bytes / 4, items, (unsigned*)fifo, wr, rd, R, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_frame(const float* fifo, const unsigned* wr, unsigned* rd, float* chunk_in, unsigned* hold, int R, int S,
+                                lh_stream_t stream) {
+    using namespace lh;
+    if (!aligned16(chunk_in) || !aligned_to(hold, 4) || !fifo_args(fifo, wr, rd, R, S)) return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_session_frame, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, fifo, wr, rd, chunk_in, hold, R, S);
+    return check_launch();
+}
+
+extern "C" int lh_session_emit_s16(const float* out, short* out16, int S, lh_stream_t stream) {
+    using namespace lh;
+    if (!aligned16(out) || !aligned16(out16) || (const void*)out == (const void*)out16 || S <= 0) return LH_ERR_ARG;
+    const int n8 = S * NSRC * HOP / 8;
+    hipLaunchKernelGGL(k_session_emit_s16, dim3((n8 + SS_NT - 1) / SS_NT), dim3(SS_NT), 0, (hipStream_t)stream,
+                       (const float4*)out, (int4*)out16, n8);
     return check_launch();
 }

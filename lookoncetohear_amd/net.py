@@ -348,14 +348,19 @@ class Net(_cabi.HipHost, nn.Module):
         return Streamer(self, batch_size, device, use_graph)
 
     def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
-                              compact: bool = False, row_buckets=None, pace: bool = False):
+                              compact: bool = False, row_buckets=None, pace: bool = False, packets: bool = False,
+                              fifo_samples: int = 2048, pcm16: bool = False):
         """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
         `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
         enrollment embedder runs beside the chunk loop and the slot opens itself on the result.
         `compact`: open listeners are kept in the leading rows and a chunk is launched for the smallest of `row_buckets`
         (ascending launch sizes ending in n_slots; default: the powers of two below n_slots, and n_slots) that holds them.
-        `pace`: `step(chunks, present=...)` holds the listeners whose chunk is late; every row owns its K / V ring position."""
-        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets, pace)
+        `pace`: `step(chunks, present=...)` holds the listeners whose chunk is late; every row owns its K / V ring position.
+        `packets` (with `pace`): `push({slot: samples [2, n]})` takes the clients' packets at any size and `step()` takes no
+        input — a device FIFO of `fifo_samples` (a power of two >= 256) per slot is re-framed into windows on the device;
+        `pcm16`: packets and output are int16."""
+        return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets, pace, packets,
+                               fifo_samples, pcm16)
 
     def _enroll_side(self, dev) -> _EnrollSide:
         return _EnrollSide(dev, self.enroll_low_priority)
@@ -1372,14 +1377,50 @@ class SessionStreamer:
     listeners with a number of launches that does not depend on it — one `lh_session_save_rows` into one `SessionSnapshotBatch`
     tensor; in `step` one `lh_session_restore_rows` and one `lh_embed_proj_ln_rows` per batch, behind one copy of an item table.
     `suspend`, `resume` and a streamer that never calls the batched methods enqueue what they always did.
+    Packets (`pace=True, packets=True`; False, the default, builds exactly the object above, launch for launch): clients do not
+    send windows, they send contiguous PCM in packets of 10 or 20 ms that arrive with jitter.  `push({slot: samples [2, n]})`
+    takes one tick's packets at any size — one fresh pinned buffer (an item table, then the samples), one asynchronous copy,
+    one launch (`lh_session_feed`) that scatters them into a device FIFO of `fifo_samples` per slot — and `step()` takes no
+    input: the chunk's first node (`lh_session_frame`) cuts a 192-sample window for every slot that holds one, writes the hold
+    words of the others itself, and everything behind `chunk_in` and `hold` is the paced streamer.  The FIFO's two sample
+    counters per slot wrap modulo 2^32 and are mirrored on the host in the same arithmetic: the host knows what every launch
+    will find (`buffered(slot)`, `ready()`, `last_present` — a tuple of S bools, the slots the last `step` consumed a chunk
+    of), the device follows, nothing is read back and no hold word travels.  A listener's output is the concatenation of
+    their rows over the steps with `last_present[slot]`, whatever the packet sizes were; a slot with two chunks buffered is
+    stepped twice (`while ss.ready(): ss.step()` catches up), a slot without one is held.  `push` raises `BufferError`, before
+    anything is enqueued for any slot, when a slot would hold more than `fifo_samples`: the device FIFO cannot overflow.
+    `flush(slot)` drops a slot's buffered input (with its next packet, or in a push of its own that `step` issues); `reset()`
+    flushes everyone.  The FIFO is transport, not listener state: `open`, `close`, `enroll`, `suspend` and `resume` do not touch
+    it and it is in no snapshot — a host that gives a slot to another client flushes it.  An idle slot is framed like any
+    other, as lock-step gates an idle slot's row.  The last chunk of a stream needs its 64 look-ahead samples: push 64 zeros
+    for the tail.  `pcm16=True`: packets are int16 (scaled by 2^-15 on the device, exact) and `step` returns int16 rows
+    (`lh_session_emit_s16`, round half even, saturating) — the bits of the fp32 path fed `pcm.float() / 32768`.
+        ss = net.make_session_streamer(64, "cuda:0", pace=True, packets=True)
+        ss.open(0, emb_a); ss.open(1, emb_b)
+        while serving:                                       # one tick: whatever arrived, then the chunks that are ready
+            ss.push({0: a.recv(160), 1: b.recv(320)})        # a 10 ms and a 20 ms client, [2, n] float32 each
+            while ss.ready():
+                y = ss.step()
+                for slot, took in enumerate(ss.last_present):
+                    if took:
+                        send(slot, y[slot])                  # [2, 128], the next 8 ms of that listener
     A snapshot is only meaningful under the weights it was taken with: that is the caller's to keep."""
     RESET, OPEN, CLOSE, GEN_SHIFT, MAX_SPANS, GEN_MASK = 1, 2, 4, 8, 32, 0x7fffff      # LH_SESSION_*
     ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
+    FEED_F32, FEED_S16, FEED_FLUSH, FEED_ITEM_WORDS = 0, 1, 1, 5                       # LH_FEED_*, lh_feed_item_t
+    HOP, WINDOW, COUNTER_MASK = 128, 192, 0xffffffff                                   # samples a chunk consumes / needs
 
     def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0, compact: bool = False,
-                 row_buckets=None, pace: bool = False):
+                 row_buckets=None, pace: bool = False, packets: bool = False, fifo_samples: int = 2048, pcm16: bool = False):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
+        if packets and not pace:
+            raise ValueError("packets are the input of a paced streamer (the device decides who is present): pace=True")
+        if pcm16 and not packets:
+            raise ValueError("pcm16 is the sample format of a packet streamer: packets=True")
+        if packets and (fifo_samples < 256 or fifo_samples & (fifo_samples - 1) or fifo_samples > 1 << 24):
+            raise ValueError(f"fifo_samples must be a power of two in [256, 2^24] (a 192-sample window while 128 more "
+                             f"arrive; the ring index is a mask), got {fifo_samples}")
         if row_buckets is not None and not compact:
             raise ValueError("row_buckets are the launch sizes of a compacting streamer: compact=True")
         if compact:
@@ -1449,6 +1490,19 @@ class SessionStreamer:
             if len(pairs[0]) > self.MAX_SPANS:
                 raise ValueError(f"{len(pairs[0]) // 2} state pairs, lh_session_end_paced takes {self.MAX_SPANS // 2}")
             self._spans_carry = [(_Span * len(p))(*[span(t) for t in p]) for p in pairs]
+        self.packets, self.pcm16, self.fifo_samples = bool(packets), bool(pcm16), int(fifo_samples)
+        if packets:
+            R = self.fifo_samples
+            self._fifo = torch.zeros(S, net.num_ch, R, device=dev)           # a ring per slot and channel
+            self._fifo_words = torch.zeros(2, S, dtype=torch.int32, device=dev)      # wr | rd: sample counters mod 2^32
+            self._wr, self._rd = [0] * S, [0] * S                             # the host's mirror of both: the device follows
+            self._flush = set()                                              # slots whose next item carries FLUSH
+            # one tick's item table and samples: at most a full ring per slot (`push` refuses more)
+            self._item_words = (self.FEED_ITEM_WORDS * S + 3) // 4 * 4
+            self._stage = torch.zeros(self._item_words + S * net.num_ch * R // (2 if pcm16 else 1), dtype=torch.int32, device=dev)
+            self.last_present = (False,) * S
+            if pcm16:
+                self.out16 = torch.zeros(S, net.n_srcs, net.stft_chunk_size, dtype=torch.int16, device=dev)
         self._gen = [0] * S                                 # generation of the slot's current opening, 0 = idle
         self._next_gen = 1
         self._pending = {}                                  # slot -> command word for the next step
@@ -1525,6 +1579,9 @@ class SessionStreamer:
             lib, stream = net._lib(st.chunk), net._stream(self.device)
             hold, pos, wpos = P(self._hold), P(self._ring[0]), P(self._ring[1])
             end, carry = self._spans_end[k], self._spans_carry[k]
+            if self.packets:                                # the windows and the hold words of this chunk, made on the device
+                lib.call("lh_session_frame", P(self._fifo), P(self._fifo_words[0]), P(self._fifo_words[1]), P(self.chunk_in),
+                         hold, self.fifo_samples, S, stream)
             if self.compact:
                 t = self._tables
                 frm, slot_of, row_of, cmd, active = P(t[0]), P(t[1]), P(t[2]), P(t[3]), P(t[5])
@@ -1547,6 +1604,8 @@ class SessionStreamer:
             else:
                 lib.call("lh_session_end_paced", A(end), len(end), A(carry), len(carry) // 2, P(self.chunk_in), P(st.out), cmd,
                          active, P(self._fault), hold, S, stream)
+            if self.pcm16:
+                lib.call("lh_session_emit_s16", P(self.out), P(self.out16), S, stream)
 
     def reset(self):
         """Every slot idle, all state zero (what a new SessionStreamer starts from).  Captures and embeddings are cancelled."""
@@ -1555,6 +1614,11 @@ class SessionStreamer:
             self._ring.zero_()
             self._hold.zero_()
             self._held = self._none_held
+        if self.packets:                                    # every slot flushed
+            self._fifo_words.zero_()
+            self._wr, self._rd = [0] * self.S, [0] * self.S
+            self._flush.clear()
+            self.last_present = (False,) * self.S
         if self.compact:
             self._tables.zero_()
             self._tables[1:3].fill_(-1)
@@ -1914,6 +1978,78 @@ class SessionStreamer:
         self._resumes.clear()
         self._resume_batches.clear()
 
+    def _packet_streamer(self):
+        if not self.packets:
+            raise ValueError("this SessionStreamer takes windows: make_session_streamer(..., pace=True, packets=True)")
+
+    def buffered(self, slot: int) -> int:
+        """Samples pushed for `slot` and not yet consumed by a `step` (host arithmetic; a pending `flush` counts as done)."""
+        self._packet_streamer()
+        slot = self._slot(slot)
+        return 0 if slot in self._flush else (self._wr[slot] - self._rd[slot]) & self.COUNTER_MASK
+
+    def ready(self) -> list:
+        """The slots that hold a whole window, 192 samples: the next `step` consumes a chunk of each (host arithmetic)."""
+        self._packet_streamer()
+        return [s for s in range(self.S) if self.buffered(s) >= self.WINDOW]
+
+    def flush(self, slot: int):
+        """Drops what `slot` has buffered: a host that gives the slot to another client does this.  Travels with the slot's
+        item of the next `push`, or in a push of its own that the next `step` issues."""
+        self._packet_streamer()
+        self._flush.add(self._slot(slot))
+
+    def push(self, packets: dict):
+        """packets {slot: CPU tensor [2, n]}, float32 (int16 in a `pcm16` streamer), any n >= 0: the clients' contiguous PCM
+        as it arrived since the last call.  One fresh pinned buffer (item table, then the samples), one asynchronous copy
+        and one `lh_session_feed` launch, whatever the number of packets; never waits for the device.  BufferError, before
+        anything is enqueued or changed for any slot, when a slot would hold more than `fifo_samples`."""
+        self._packet_streamer()
+        S, R, M, dtype = self.S, self.fifo_samples, self.COUNTER_MASK, torch.int16 if self.pcm16 else torch.float32
+        nch, wr, rd, flushed = self.chunk_in.shape[1], self._wr, self._rd, self._flush
+        todo = []
+        for slot, x in packets.items():
+            slot = self._slot(int(slot))
+            if not isinstance(x, torch.Tensor) or x.is_cuda or x.dtype != dtype or x.dim() != 2 or x.shape[0] != nch:
+                raise ValueError(f"slot {slot}: a packet is a CPU {dtype} tensor [{nch}, n]")
+            n = x.shape[1]
+            have = 0 if slot in flushed else (wr[slot] - rd[slot]) & M
+            if have + n > R:
+                raise BufferError(f"slot {slot}: {have} samples buffered + {n} pushed > fifo_samples = {R}: "
+                                  "step() first (while ss.ready(): ss.step()), or flush(slot)")
+            if n or slot in flushed:
+                todo.append((slot, x, n))
+        if flushed:
+            todo += [(slot, None, 0) for slot in sorted(flushed - {t[0] for t in todo})]
+        if not todo:
+            return
+        net, st = self.net, self._st
+        per = 2 if self.pcm16 else 1                        # samples per 32-bit word
+        total = sum(nch * n for _, _, n in todo)
+        used = self._item_words + (total + per - 1) // per
+        src = net._host_words(used, self.device)            # FRESH, for the reason `step` gives for its command words
+        buf = src.numpy()
+        table = buf[:self.FEED_ITEM_WORDS * len(todo)].reshape(-1, self.FEED_ITEM_WORDS)
+        samples = buf[self._item_words:].view(np.int16 if self.pcm16 else np.float32)
+        off = 0
+        for i, (slot, x, n) in enumerate(todo):
+            flush = slot in flushed
+            if flush:
+                wr[slot] = rd[slot] = 0
+            at = wr[slot]
+            table[i] = (slot, off, n, at - (1 << 32) if at >> 31 else at, self.FEED_FLUSH if flush else 0)
+            if n:
+                samples[off:off + nch * n].reshape(nch, n)[...] = x.numpy()
+            wr[slot] = (at + n) & M
+            off += nch * n
+        flushed.clear()
+        self._stage[:used].copy_(src, non_blocking=True)
+        with torch.no_grad(), net._device_ctx(st.chunk):
+            net._lib(st.chunk).call("lh_session_feed", self._stage[self._item_words:].data_ptr(), total * (4 // per),
+                                    self.FEED_S16 if self.pcm16 else self.FEED_F32, self._stage.data_ptr(), len(todo),
+                                    self._fifo.data_ptr(), self._fifo_words[0].data_ptr(), self._fifo_words[1].data_ptr(), R, S,
+                                    net._stream(self.device))
+
     def set_embedding(self, slot: int, embed: torch.Tensor):
         """Re-target an open slot ("look once" at another speaker): the carried state is kept."""
         self._slot(slot)
@@ -1955,18 +2091,34 @@ class SessionStreamer:
                     self._enrolled[s] = out[i]
                     self._open(s, out[i])
 
-    def step(self, chunks: torch.Tensor, present=None) -> torch.Tensor:
+    def step(self, chunks: Optional[torch.Tensor] = None, present=None) -> torch.Tensor:
         """chunks [S, 2, 192] (rows of idle slots are ignored) -> [S, 2, 128] (rows of idle slots are zeros); a view the next
         `step` overwrites.  Never raises for a slot's fault: see `faults()`.
         `present` (a paced streamer only): a length-S sequence or CPU bool tensor, false = the slot is held for this step —
-        its row of `chunks` is ignored, its output row is zeros, its state stays.  None: everyone is present."""
+        its row of `chunks` is ignored, its output row is zeros, its state stays.  None: everyone is present.
+        A packet streamer takes neither: `step()` consumes one window of every slot that has 192 samples buffered, holds the
+        others, and says which in `last_present`; the output is int16 when the streamer was built with `pcm16`."""
         st = self._st
+        if self.packets:
+            if chunks is not None or present is not None:
+                raise ValueError("a packet streamer gets its samples through push(): step() takes no chunks and no `present`")
+        elif chunks is None:
+            raise ValueError("step() without chunks needs a packet streamer: make_session_streamer(..., pace=True, packets=True)")
         if present is not None and not self.pace:
             raise ValueError("`present` needs a paced streamer: make_session_streamer(..., pace=True)")
         st._check_repacked()
         st._check_versions()
         self.poll()
-        if self.pace:
+        if self.packets:
+            if self._flush:                                 # a flush nobody pushed behind travels on its own
+                self.push({})
+            # what lh_session_frame will find and do, in the same arithmetic: nothing travels, nothing is read back
+            wr, rd, M = self._wr, self._rd, self.COUNTER_MASK
+            self.last_present = took = tuple((w - r) & M >= self.WINDOW for w, r in zip(wr, rd))
+            for s, t in enumerate(took):
+                if t:
+                    rd[s] = (rd[s] + self.HOP) & M
+        elif self.pace:
             held = self._none_held
             if present is not None:
                 held = tuple(not p for p in (present.tolist() if isinstance(present, torch.Tensor) else present))
@@ -2000,7 +2152,8 @@ class SessionStreamer:
             self._ewords[0].copy_(src, non_blocking=True)
         if self._resumes:
             self._restore()
-        self.chunk_in.copy_(chunks)
+        if not self.packets:
+            self.chunk_in.copy_(chunks)
         with torch.no_grad():
             if self.graphs is None:
                 self._body(st.parity, self.last_rows)
@@ -2009,4 +2162,4 @@ class SessionStreamer:
             else:
                 self.graphs[st.parity].replay()
         st.parity ^= 1
-        return self.out
+        return self.out16 if self.pcm16 else self.out

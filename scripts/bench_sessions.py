@@ -33,6 +33,14 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         returns them through `resume_many`, steady steps, and the same two steps through the loops of `suspend` / `resume`.
         The batched step has to be cheaper than the loop by more than three times the scatter of the steady blocks.  --tiles:
         also the batched steps at the largest k under each tile count per (item, section) (lh_set_tuning key 18).
+    python scripts/bench_sessions.py --packets [--batches 1,64] [--out profiles/packets_cost.txt]
+        what the packet front costs, in DEVICE time per step as above (the events enclose `push` and the step it precedes, so
+        the copy and the feed launch are counted), a packet-fed streamer against today's paced streamer, blocks of the two
+        interleaved in one run: (a) every second slot alternately late, so presence changes in every step — 128-sample packets
+        for the slots that are due against `step(chunks, present)` with the same mask, windows on the device and windows in
+        pinned host memory; (b) everyone present.  The loop waits for every step, so the host's time inside `push` is in the
+        interval; the `pipelined` arm enqueues the push for step i + 1 behind step i instead, as a host does that takes
+        packets while the chunk runs.  `scatter` is the spread of the paced blocks' p50.
 """
 import argparse
 import json
@@ -352,6 +360,111 @@ def suspend_bench(net, args):
             f.write(text + "\n")
 
 
+def packets_bench(net, args):
+    reps, N = 4, 80000
+    lines = [f"packet front, device time per step (HIP events around push + step, or around step(chunks, present)), {args.steps} "
+             f"steps per figure in {reps} interleaved blocks after {args.warmup} warm-up; the yardstick is the paced "
+             f"SessionStreamer of the same run fed explicit windows"]
+    for B in [int(b) for b in args.batches.split(",")]:
+        d = synth.batch(list(range(B)), N)
+        host = torch.nn.functional.pad(d["mixture"], (0, 64)).pin_memory()
+        mix = host.to(DEV)
+        emb = d["embedding_gt"][:, 0].to(DEV)
+        chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+        chunks_host = [host[:, :, i * 128:i * 128 + 192].contiguous().pin_memory() for i in range(625)]
+        paced, fed = net.make_session_streamer(B, DEV, pace=True), net.make_session_streamer(B, DEV, pace=True, packets=True)
+        for ss in (paced, fed):
+            for s in range(B):
+                ss.open(s, emb[s])
+        even = [s % 2 == 0 for s in range(B)]
+        flip = [even, [not p for p in even]]
+        pos, push_us = [0] * B, []
+
+        def next_packets(due):
+            """The next 128 samples of every slot that is due, as a client sends them: a buffer of their own."""
+            packets = {}
+            for s, d in enumerate(due):
+                if d:
+                    packets[s] = host[s, :, pos[s]:pos[s] + 128].contiguous()
+                    pos[s] = (pos[s] + 128) % N
+            return packets
+
+        def fed_steps(n, due_of, i0, pipelined=False):
+            """n steps of the packet streamer; the slots of `due_of(i)` get their next 128 samples ahead of step i.  The packets
+            exist before the interval starts.  Timed is push + step — or, `pipelined`, step i and then the push for step i + 1,
+            which the host assembles while the device runs the chunk: `push` never waits."""
+            ms = []
+            if pipelined:
+                fed.push(next_packets(due_of(i0)))
+            for i in range(i0, i0 + n):
+                ahead = pipelined and i + 1 < i0 + n
+                packets = next_packets(due_of(i + 1)) if ahead else None if pipelined else next_packets(due_of(i))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                t0 = time.perf_counter()
+                if not pipelined:
+                    fed.push(packets)
+                    push_us.append(1e6 * (time.perf_counter() - t0))
+                fed.step()
+                present = list(fed.last_present)
+                if ahead:
+                    fed.push(packets)
+                e1.record()
+                e1.synchronize()
+                assert present == list(due_of(i)), i
+                ms.append(e0.elapsed_time(e1))
+            return ms
+
+        def prime():
+            """Every slot holds the 64 look-ahead samples: 128 more make a window, and a step leaves 64 again."""
+            for s in range(B):
+                fed.flush(s)
+            fed.push({s: host[s, :, pos[s]:pos[s] + 64] for s in range(B)})
+            for s in range(B):
+                pos[s] += 64
+
+        everyone = [True] * B
+        arms = [("(a) presence changes every step", lambda i: flip[i & 1]), ("(b) everyone present", lambda i: everyone)]
+        for name, due_of in arms:
+            prime()
+            i_fed = 0
+            fed_steps(args.warmup, due_of, i_fed)
+            i_fed += args.warmup
+            mask_of = (lambda i: None) if due_of(0) is everyone else due_of
+            dev_steps_present(paced, chunks, args.warmup, mask_of)
+            ms, p50s = {"paced": [], "paced, host windows": [], "packets": [], "packets, pipelined": []}, []
+            del push_us[:]
+            for rep in range(reps):
+                n = args.steps // reps
+                blk = dev_steps_present(paced, chunks, n, mask_of)
+                ms["paced"] += blk
+                p50s.append(pct(blk, 0.5))
+                ms["paced, host windows"] += dev_steps_present(paced, chunks_host, n, mask_of)
+                ms["packets"] += fed_steps(n, due_of, i_fed)
+                ms["packets, pipelined"] += fed_steps(n, due_of, i_fed + n, pipelined=True)
+                i_fed += 2 * n
+            torch.cuda.synchronize()
+            assert paced.faults() == [] and fed.faults() == [] and len(fed.active) == B
+            r = {k: stats(v) for k, v in ms.items()}
+            scatter = max(p50s) - min(p50s)
+            for k in ("paced, host windows", "packets", "packets, pipelined"):
+                cost = r[k]["p50_ms"] - r["paced"]["p50_ms"]
+                lines.append(f"{name:32s} S={B:3d}   paced, windows on the device: p50 {r['paced']['p50_ms']:.4f} p99 "
+                             f"{r['paced']['p99_ms']:.4f} ms   {k}: p50 {r[k]['p50_ms']:.4f} p99 {r[k]['p99_ms']:.4f} ms   "
+                             f"difference {1e3 * cost:+.1f} us ({100.0 * cost / r['paced']['p50_ms']:+.1f} %), scatter of the "
+                             f"paced blocks {1e3 * scatter:.1f} us: {'WITHIN' if abs(cost) <= 3 * scatter else 'NOT within'} "
+                             f"three times the scatter")
+            cost = r["packets"]["p50_ms"] - r["paced, host windows"]["p50_ms"]
+            lines.append(f"{name:32s} S={B:3d}   packets minus paced with host windows {1e3 * cost:+.1f} us; host time inside "
+                         f"push (table, {sum(due_of(0))} or {sum(due_of(1))} packets, copy, launch): p50 {pct(push_us, 0.5):.1f} us")
+        del paced, fed
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def suspend_many_bench(net, args):
     from lookoncetohear_amd import _cabi
 
@@ -441,6 +554,7 @@ def main():
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--suspend", action="store_true")
     ap.add_argument("--suspend-many", action="store_true")
+    ap.add_argument("--packets", action="store_true")
     ap.add_argument("--many", default="1,8,64")
     ap.add_argument("--tiles", default="")
     ap.add_argument("--slots", type=int, default=64)
@@ -467,6 +581,8 @@ def main():
         return suspend_bench(net, args)
     if args.suspend_many:
         return suspend_many_bench(net, args)
+    if args.packets:
+        return packets_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
