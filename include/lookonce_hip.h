@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (22); bumped on any signature change. */
+/* ABI version of this header (23); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -759,6 +759,46 @@ int lh_session_feed(const void* staging, unsigned long long staging_bytes, int f
 int lh_session_frame(const float* fifo, const unsigned* wr, unsigned* rd, float* chunk_in, unsigned* hold, int R, int S,
                      lh_stream_t stream);
 int lh_session_emit_s16(const float* out, short* out16, int S, lh_stream_t stream);
+
+/* Client rate (ABI 23): polyphase sinc resampling, offline for the data pipeline and per slot for a packet host whose clients
+ * capture and play at their own rate (48, 32, 24, 8 kHz ...).  The arithmetic is torchaudio's published `sinc_interp_hann`
+ * algorithm, restated (csrc/lh_resample.h; lookoncetohear_amd/resample.py makes the bank):
+ *     g = gcd(orig, new), o = orig / g, n = new / g, K = 2 width + o
+ *     y[q n + p] = sum_{k < K} xpad[q o + k] * bank[p][k]          xpad = width zeros, x, width + o zeros
+ *     len(y) = ceil(n len(x) / o)
+ *   bank      [n][K] fp32 in device memory, made in fp64 on the host and cast.
+ * Every kernel accumulates alike — one fp32 accumulator from +0, one fmaf per tap, ascending k — so a stream that went through
+ * the session nodes in packets of any size carries the bits of lh_resample of the whole stream.
+ *   lh_resample   x [rows][n_in] (16-byte aligned) -> y [rows][n_out], n_out = ceil(n_in n / o); one launch.
+ *   lh_session_resample_in   (an eager launch, behind the lh_session_feed of the same tick)  lh_session_feed, unchanged, lands the
+ *              client-rate packets in a second ring raw [S][2][R_in] with two counters of its own; this launch turns whole
+ *              blocks of it into 16 kHz samples of the fifo of the packets section and stores wr[slot] — the only other writer of
+ *              that word.  items: n_items >= 1 entries in DEVICE memory.  Item i makes items[i].blocks blocks (blocks * n
+ *              samples per channel) for items[i].slot: sample j goes to fifo[slot][ch][(wr + j) & (R - 1)], its taps are raw
+ *              samples [tap + (j / n) o, tap + (j / n) o + K) at ring index counter & (R_in - 1); then wr[slot] = wr + blocks n.
+ *              `wr` is the slot's 16 kHz write counter before the item, `tap` the raw counter of the first block's first tap —
+ *              both the HOST's mirrors, modulo 2^32: the kernel reads no counter.  A stream starts at raw counter 0 with
+ *              tap = -width: the host zeroes the slot's raw ring when it flushes it, and those zeros are the left pad.  The host
+ *              hands out a block only when all K of its samples have been pushed.  Skipped whole: an item whose slot is outside
+ *              [0, S), whose blocks are negative, make more than R samples or read more than R_in.
+ *   lh_session_resample_out  (a graph node after lh_session_end[_rows]_paced, one workgroup per slot; in a client-rate host it
+ *              takes the place of lh_session_emit_s16)  out [S][2][128] at 16 kHz and tail [S][2][T], T = width + D o,
+ *              D = ceil((width + o) / o), zero at start -> out_client [S][2][128 n / o]; o must divide 128.  Step t emits
+ *              blocks [Q t - D, Q (t + 1) - D), Q = 128 / o, of the resampled stream of rows: lh_resample of D o zeros followed by
+ *              the rows, a fixed delay of D o samples at 16 kHz.  Then the tail is the last T samples of (tail, row).
+ *              format: LH_FEED_F32 (float rows) or LH_FEED_S16 (int16 rows, the rounding of lh_session_emit_s16).
+ *              hold[s] != 0: a zero row, and the slot's tail is not advanced.
+ * LH_ERR_ARG: null or misaligned pointer (x, raw, fifo, out, out_client: 16 bytes), aliased buffers, o or n outside [1, 4096],
+ * width < 1 or o + 2 width + 8 > 8192, n_out not ceil(n_in n / o), rows outside [1, 65535], R or R_in not a power of two in
+ * [256, 2^24], R_in < K (too few samples for one block), n_items outside [1, 65535], S <= 0, an unknown format, o not a divisor
+ * of 128 or T > 896 (lh_session_resample_out).  None of the three allocates, synchronises or reads device memory on the host. */
+typedef struct { int slot; int blocks; unsigned wr; unsigned tap; } lh_resample_item_t;   /* 16 bytes */
+int lh_resample(const float* x, float* y, const float* bank, int rows, int n_in, int n_out, int o, int n, int width,
+                lh_stream_t stream);
+int lh_session_resample_in(const float* raw, int R_in, const lh_resample_item_t* items, int n_items, float* fifo, unsigned* wr,
+                           int R, int S, const float* bank, int o, int n, int width, lh_stream_t stream);
+int lh_session_resample_out(const float* out, float* tail, const unsigned* hold, void* out_client, int format, int S,
+                            const float* bank, int o, int n, int width, lh_stream_t stream);
 
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.

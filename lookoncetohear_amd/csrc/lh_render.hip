@@ -12,7 +12,10 @@
 //   k_fft_conv     the same convolution by overlap-save FFT for 1024 <= Lh <= 4097 taps (BRIR-length responses)
 //   k_mix_peak     peak of |sum of sources| per utterance (order-independent: atomicMax on the float bit pattern)
 //   k_mix_apply    events / norm (when norm > 1), mixture = ((e0 + e1) + e2) + noise in the reference's order, target
+//   k_resample     polyphase sinc resampling of whole rows (the reference's last dataset step, torchaudio Resample, and its
+//                  simulators' impulse-response resampling): lh_resample.h has the arithmetic
 #include "lh_common.h"
+#include "lh_resample.h"
 
 namespace lh {
 
@@ -146,6 +149,53 @@ __global__ void __launch_bounds__(256) k_mix_apply(float* __restrict__ ev, const
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Resampling of whole rows: grid (tiles of TB output blocks, rows), block 256.  A workgroup stages the input span of its
+// tile in (dynamic) LDS — x[q0 o - width, (q0 + TB) o + width), zeros outside the row, 16 bytes at a time where the row's length
+// keeps every row aligned — and the bank too when it is small (n K <= RS_BANK; a large bank, 441/160, stays in L2).  Thread e owns
+// output e of the tile: consecutive threads store consecutive samples, and for a decimator they read LDS at stride o.
+// Bandwidth-bound by design: K fmaf per output against 4 bytes stored.  Plain scalar fp32, one dependent chain per thread.
+// ------------------------------------------------------------------------------------------------------
+constexpr int RS_NT = 256, RS_BANK = 4096, RS_TILE_OUT = 1024;
+__global__ void __launch_bounds__(RS_NT) k_resample(const float* __restrict__ x, float* __restrict__ y,
+                                                    const float* __restrict__ bank, int n_in, int n_out, int o, int n, int width,
+                                                    int TB, int xs_floats, int bank_lds) {
+    // dynamic LDS, sized by lh_resample to what the ratio needs (12.5 KiB for 3/1): the staging is latency, so occupancy counts
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float* xs = reinterpret_cast<float*>(lds4);               // xs_floats (a multiple of 4, <= RS_SPAN), then the bank
+    float* bs = xs + xs_floats;
+    const int tid = threadIdx.x, K = 2 * width + o;
+    const long q0 = (long)blockIdx.x * TB;
+    const float* xr = x + (long)blockIdx.y * n_in;
+    const long g0 = q0 * o - width;                           // the tile's first input sample (negative: the left pad)
+    const long ga = g0 & ~3L;                                 // ... rounded down to a float4 of the row
+    const int shift = (int)(g0 - ga), span = TB * o + 2 * width + shift;      // <= xs_floats - 4
+    const bool vec = !(n_in & 3);                             // x is 16-byte aligned: then so is every row
+    for (int v = tid; 4 * v < span; v += RS_NT) {
+        const long g = ga + 4L * v;
+        float4 t;
+        if (vec && g >= 0 && g + 3 < n_in) {
+            t = *reinterpret_cast<const float4*>(xr + g);
+        } else {
+            t.x = (g >= 0 && g < n_in) ? xr[g] : 0.f;
+            t.y = (g + 1 >= 0 && g + 1 < n_in) ? xr[g + 1] : 0.f;
+            t.z = (g + 2 >= 0 && g + 2 < n_in) ? xr[g + 2] : 0.f;
+            t.w = (g + 3 >= 0 && g + 3 < n_in) ? xr[g + 3] : 0.f;
+        }
+        *reinterpret_cast<float4*>(xs + 4 * v) = t;
+    }
+    if (bank_lds)
+        for (int i = tid; i < n * K; i += RS_NT) bs[i] = bank[i];
+    __syncthreads();
+    const float* rows = bank_lds ? bs : bank;
+    float* yr = y + (long)blockIdx.y * n_out;
+    for (int e = tid; e < TB * n; e += RS_NT) {
+        const int ql = e / n, p = e - ql * n;
+        const long j = q0 * n + e;
+        if (j < n_out) yr[j] = resample_dot(TapSpan{xs + shift + ql * o}, rows + p * K, K);
+    }
+}
+
 }  // namespace lh
 
 // Renders B utterances of S1 mono rows each (sources first, the noise bed LAST) to two ears and mixes them.
@@ -174,5 +224,24 @@ extern "C" int lh_render_binaural(const float* src, const float* rir, const floa
     const int chunks = (int)((2L * N + 256 * 8 - 1) / (256 * 8));
     hipLaunchKernelGGL(k_mix_peak, dim3(chunks, B), dim3(256), 0, st, events, peak, S1, N);
     hipLaunchKernelGGL(k_mix_apply, dim3(chunks, B), dim3(256), 0, st, events, peak, tgt_idx, mixture, target, S1, N);
+    return check_launch();
+}
+
+// Resamples `rows` rows of n_in samples by n / o: y[r][q n + p] = sum_k xpad[r][q o + k] bank[p][k], n_out = ceil(n_in n / o).
+extern "C" int lh_resample(const float* x, float* y, const float* bank, int rows, int n_in, int n_out, int o, int n, int width,
+                           lh_stream_t stream) {
+    using namespace lh;
+    const auto aligned = [](const void* p, unsigned a) { return p && !((unsigned long long)(size_t)p & (a - 1u)); };
+    if (!aligned(x, 16) || !aligned(y, 4) || !aligned(bank, 4) || x == y || rows < 1 || rows > 65535 || n_in < 1 ||
+        !resample_ratio_ok(o, n, width) || ((long)n_in * n + o - 1) / o != (long)n_out)
+        return LH_ERR_ARG;
+    const int by_out = RS_TILE_OUT / n < 1 ? 1 : RS_TILE_OUT / n, by_span = (RS_SPAN - 2 * width - 8) / o;
+    const int TB = by_out < by_span ? by_out : by_span;       // >= 1: resample_ratio_ok
+    const long blocks = ((long)n_out + n - 1) / n, tiles = (blocks + TB - 1) / TB;
+    if (tiles > 0x7fffffffL) return LH_ERR_ARG;
+    const int xs_floats = (TB * o + 2 * width + 8 + 3) & ~3, bank_lds = (long)n * (2 * width + o) <= RS_BANK ? 1 : 0;
+    const unsigned lds_bytes = 4u * (unsigned)(xs_floats + (bank_lds ? n * (2 * width + o) : 0));       // <= 48 KiB
+    hipLaunchKernelGGL(k_resample, dim3((unsigned)tiles, rows), dim3(RS_NT), lds_bytes, (hipStream_t)stream, x, y, bank, n_in, n_out,
+                       o, n, width, TB, xs_floats, bank_lds);
     return check_launch();
 }

@@ -18,6 +18,7 @@
 // Reference: tfgridnet_causal.py:505-512 (intra_norm + intra_rnn); output in the unfused layout [rows][128] consumed
 // by lh_linear_res.
 #include "lh_quad.h"
+#include "lh_resample.h"
 
 namespace lh {
 
@@ -1075,6 +1076,79 @@ __global__ void __launch_bounds__(SS_NT) k_session_emit_s16(const float4* __rest
     out16[i] = p;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Client rate (ABI 23): the packet host at the client's own sample rate.  The packets land, through k_session_feed unchanged, in a
+// second ring raw[S][2][R_in] at the client rate (with two counters of its own); k_session_resample_in turns whole blocks of it
+// into 16 kHz samples of the FIFO above, and k_session_resample_out turns every chunk's 16 kHz row into a row at the client
+// rate.  Both call resample_dot of lh_resample.h, so what they make equals lh_resample of the whole stream, bit for bit.
+//   k_session_resample_in   (eager, behind the feed of the same push; grid tile x item)  An item is (slot, the 16 kHz write
+//                    counter before it, whole output blocks, the raw counter of the first block's first tap) — all the HOST's
+//                    mirrors, modulo 2^32: the kernel reads no counter, so the workgroups of an item have nothing to race on.
+//                    Output j of the item is block j / n, phase j % n; its taps are raw samples [tap + (j / n) o, ... + K).  The
+//                    stream's left pad of `width` zeros is the zeroed ring below counter 0.  One thread stores wr[slot].
+//   k_session_resample_out  (a graph node after the end kernel, one workgroup per slot)  [tail | row] of a slot and channel is
+//                    staged in LDS, T = width + D o carried samples and the chunk's 128; output j of the step reads taps
+//                    [(j / n) o, (j / n) o + K) of it; the last T samples become the tail.  A held slot: a zero row, the tail
+//                    stays.  The zeroed tail at start is the left pad and the fixed delay of D blocks in one.
+// ------------------------------------------------------------------------------------------------------
+constexpr int RI_NT = 256, RI_MAX_TILES = 16;
+__global__ void __launch_bounds__(RI_NT) k_session_resample_in(const float* __restrict__ raw, int R_in,
+                                                               const lh_resample_item_t* __restrict__ items,
+                                                               float* __restrict__ fifo, unsigned* wr, int R, int S,
+                                                               const float* __restrict__ bank, int o, int n, int width) {
+    const int tid = threadIdx.x, tile = blockIdx.x, ntile = gridDim.x, K = 2 * width + o;
+    const lh_resample_item_t it = items[blockIdx.y];
+    // served or skipped whole, by every workgroup alike and before an address is formed
+    if ((unsigned)it.slot >= (unsigned)S || it.blocks < 0 || (long)it.blocks * n > R ||
+        (it.blocks > 0 && (long)(it.blocks - 1) * o + K > R_in))
+        return;
+    const int per = it.blocks * n;                             // new 16 kHz samples per channel
+    const unsigned mask = (unsigned)R - 1u, mask_in = (unsigned)R_in - 1u;
+    const float* ring_in = raw + (long)it.slot * NMIC * R_in;
+    float* ring = fifo + (long)it.slot * NMIC * R;
+    for (int e = tile * RI_NT + tid; e < NMIC * per; e += ntile * RI_NT) {
+        const int ch = e >= per ? 1 : 0, j = e - ch * per, q = j / n, p = j - q * n;
+        const TapRing tap{ring_in + (long)ch * R_in, it.tap + (unsigned)q * (unsigned)o, mask_in};
+        ring[(long)ch * R + ((it.wr + (unsigned)j) & mask)] = resample_dot(tap, bank + p * K, K);
+    }
+    if (tile == 0 && tid == 0) wr[it.slot] = it.wr + (unsigned)per;
+}
+
+constexpr int RO_NT = 256, RO_XS = 1024;       // staged samples per channel: tail + chunk
+template <bool S16>
+__global__ void __launch_bounds__(RO_NT) k_session_resample_out(const float* __restrict__ out, float* __restrict__ tail,
+                                                                const unsigned* __restrict__ hold, void* __restrict__ out_client,
+                                                                const float* __restrict__ bank, int o, int n, int width, int T) {
+    __shared__ float xs[NSRC][RO_XS];
+    const int s = blockIdx.x, tid = threadIdx.x, K = 2 * width + o, hop_c = HOP / o * n, len = T + HOP;
+    float* row32 = reinterpret_cast<float*>(out_client) + (long)s * NSRC * hop_c;
+    short* row16 = reinterpret_cast<short*>(out_client) + (long)s * NSRC * hop_c;
+    if (hold[s] != 0u) {                                       // block-uniform
+        for (int e = tid; e < NSRC * hop_c; e += RO_NT) {
+            if constexpr (S16) row16[e] = 0;
+            else row32[e] = 0.f;
+        }
+        return;
+    }
+    float* tl = tail + (long)s * NSRC * T;
+    const float* row = out + (long)s * NSRC * HOP;
+    for (int i = tid; i < NSRC * len; i += RO_NT) {
+        const int ch = i / len, j = i - ch * len;
+        xs[ch][j] = j < T ? tl[ch * T + j] : row[ch * HOP + j - T];
+    }
+    __syncthreads();                                           // the old tail has been read by everyone
+    for (int e = tid; e < NSRC * hop_c; e += RO_NT) {
+        const int ch = e / hop_c, j = e - ch * hop_c, q = j / n, p = j - q * n;
+        const float v = resample_dot(TapSpan{xs[ch] + q * o}, bank + p * K, K);
+        if constexpr (S16) row16[e] = (short)emit_s16(v);
+        else row32[e] = v;
+    }
+    for (int i = tid; i < NSRC * T; i += RO_NT) {
+        const int ch = i / T, j = i - ch * T;
+        tl[i] = xs[ch][HOP + j];
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -1426,5 +1500,42 @@ extern "C" int lh_session_emit_s16(const float* out, short* out16, int S, lh_str
     const int n8 = S * NSRC * HOP / 8;
     hipLaunchKernelGGL(k_session_emit_s16, dim3((n8 + SS_NT - 1) / SS_NT), dim3(SS_NT), 0, (hipStream_t)stream,
                        (const float4*)out, (int4*)out16, n8);
+    return check_launch();
+}
+
+// ---- client rate (ABI 23) -----------------------------------------------------------------------------------------------------
+namespace lh {
+// carried 16 kHz samples of the out node: the taps below a step's first block, T = width + D o with D = ceil((width + o) / o)
+static int resample_out_tail(int o, int width) { return width + (width + 2 * o - 1) / o * o; }
+}  // namespace lh
+
+extern "C" int lh_session_resample_in(const float* raw, int R_in, const lh_resample_item_t* items, int n_items, float* fifo,
+                                      unsigned* wr, int R, int S, const float* bank, int o, int n, int width, lh_stream_t stream) {
+    using namespace lh;
+    const auto ring_ok = [](int r) { return r >= 256 && r <= (1 << 24) && !(r & (r - 1)); };
+    if (!aligned16(raw) || !aligned16(fifo) || (const void*)raw == (const void*)fifo || !aligned_to(items, 4) || !aligned_to(wr, 4) ||
+        !aligned_to(bank, 4) || n_items < 1 || n_items > 65535 || S <= 0 || !ring_ok(R) || !ring_ok(R_in) ||
+        !resample_ratio_ok(o, n, width) || 2 * width + o > R_in)
+        return LH_ERR_ARG;
+    const int want = NMIC * R / (4 * RI_NT), tiles = want < 1 ? 1 : (want > RI_MAX_TILES ? RI_MAX_TILES : want);
+    hipLaunchKernelGGL(k_session_resample_in, dim3(tiles, n_items), dim3(RI_NT), 0, (hipStream_t)stream, raw, R_in, items, fifo, wr,
+                       R, S, bank, o, n, width);
+    return check_launch();
+}
+
+extern "C" int lh_session_resample_out(const float* out, float* tail, const unsigned* hold, void* out_client, int format, int S,
+                                       const float* bank, int o, int n, int width, lh_stream_t stream) {
+    using namespace lh;
+    if ((format != LH_FEED_F32 && format != LH_FEED_S16) || !aligned16(out) || !aligned_to(tail, 4) || !aligned_to(hold, 4) ||
+        !aligned16(out_client) || (const void*)out == (const void*)out_client || (const void*)tail == (const void*)out ||
+        !aligned_to(bank, 4) || S <= 0 || !resample_ratio_ok(o, n, width) || HOP % o || resample_out_tail(o, width) + HOP > RO_XS)
+        return LH_ERR_ARG;
+    const int T = resample_out_tail(o, width);
+    if (format == LH_FEED_S16)
+        hipLaunchKernelGGL(k_session_resample_out<true>, dim3(S), dim3(RO_NT), 0, (hipStream_t)stream, out, tail, hold, out_client,
+                           bank, o, n, width, T);
+    else
+        hipLaunchKernelGGL(k_session_resample_out<false>, dim3(S), dim3(RO_NT), 0, (hipStream_t)stream, out, tail, hold, out_client,
+                           bank, o, n, width, T);
     return check_launch();
 }

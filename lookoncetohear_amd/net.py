@@ -349,7 +349,7 @@ class Net(_cabi.HipHost, nn.Module):
 
     def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
                               compact: bool = False, row_buckets=None, pace: bool = False, packets: bool = False,
-                              fifo_samples: int = 2048, pcm16: bool = False):
+                              fifo_samples: int = 2048, pcm16: bool = False, client_rate: int = 16000):
         """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
         `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
         enrollment embedder runs beside the chunk loop and the slot opens itself on the result.
@@ -358,9 +358,11 @@ class Net(_cabi.HipHost, nn.Module):
         `pace`: `step(chunks, present=...)` holds the listeners whose chunk is late; every row owns its K / V ring position.
         `packets` (with `pace`): `push({slot: samples [2, n]})` takes the clients' packets at any size and `step()` takes no
         input — a device FIFO of `fifo_samples` (a power of two >= 256) per slot is re-framed into windows on the device;
-        `pcm16`: packets and output are int16."""
+        `pcm16`: packets and output are int16.
+        `client_rate` (with `packets`): the clients' sample rate, a multiple of 125 Hz; `push` takes and `step` returns PCM at
+        that rate, resampled on the device on the way in and on the way out."""
         return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets, pace, packets,
-                               fifo_samples, pcm16)
+                               fifo_samples, pcm16, client_rate)
 
     def _enroll_side(self, dev) -> _EnrollSide:
         return _EnrollSide(dev, self.enroll_low_priority)
@@ -1395,6 +1397,24 @@ class SessionStreamer:
     other, as lock-step gates an idle slot's row.  The last chunk of a stream needs its 64 look-ahead samples: push 64 zeros
     for the tail.  `pcm16=True`: packets are int16 (scaled by 2^-15 on the device, exact) and `step` returns int16 rows
     (`lh_session_emit_s16`, round half even, saturating) — the bits of the fp32 path fed `pcm.float() / 32768`.
+    Client rate (`packets=True, client_rate=48000`; 16000, the default, builds exactly the object above, launch for launch):
+    headsets and WebRTC stacks capture and play at 48 kHz, some at 32, 24 or 8.  `push` takes `[2, n]` at the client's rate and
+    `step()` returns `[S, 2, hop_client]`, `hop_client = 128 * client_rate / 16000` samples at that rate (fp32, or int16 with
+    `pcm16`) — resampled on the device with the arithmetic of `resample.Resampler` (torchaudio's `sinc_interp_hann`, one fp32
+    inner product that every kernel shares): the packets land through `lh_session_feed` in a second per-slot ring at the client
+    rate, `lh_session_resample_in` (one more launch of the same `push`, its items in the same copy) turns whole blocks of it into
+    16 kHz samples of the FIFO, and `lh_session_resample_out`, the chunk's last node, turns the 16 kHz rows into client rows.
+    What a listener hears equals `Resampler(client_rate, 16000)` of their whole stream, served by a 16 kHz packet streamer, then
+    `Resampler(16000, client_rate)` of `delay_out` zeros followed by the rows — bit for bit, whatever the packet sizes.  Rates
+    are multiples of 125 Hz (a chunk is then a whole number of client samples): 8000, 24000, 32000, 40000, 48000, 96000 ...;
+    44100 is refused — resample such a stream with `Resampler` first.  `fifo_samples`, `buffered`, `ready`, `last_present` and
+    `BufferError` keep their meaning in 16 kHz samples: the host mirrors the resampler's block arithmetic in integers.
+    Added latency: a 16 kHz block is made when its `lookahead_in = width + o - 1` later client samples have been pushed (48 kHz:
+    21 samples, 0.44 ms), and the output is `delay_out` 16 kHz samples late (toward 48 kHz: 8 samples, 0.5 ms); the tail of a
+    stream needs `lookahead_in` zeros pushed behind it (and the 64 look-ahead samples of the last chunk, at the client's rate).
+    The raw ring and the output tail are transport like the FIFO: in no snapshot, untouched by `open`, `close`, `suspend` and
+    `resume`; `flush(slot)` and `reset()` clear them, so a flushed slot's stream starts from silence, as torchaudio's left pad
+    does.  Enrollment keeps recording the 16 kHz `chunk_in`.
         ss = net.make_session_streamer(64, "cuda:0", pace=True, packets=True)
         ss.open(0, emb_a); ss.open(1, emb_b)
         while serving:                                       # one tick: whatever arrived, then the chunks that are ready
@@ -1409,11 +1429,20 @@ class SessionStreamer:
     ARM, CANCEL, ENROLL_FAULT = 1, 2, 0x80000000                                       # LH_ENROLL_*
     FEED_F32, FEED_S16, FEED_FLUSH, FEED_ITEM_WORDS = 0, 1, 1, 5                       # LH_FEED_*, lh_feed_item_t
     HOP, WINDOW, COUNTER_MASK = 128, 192, 0xffffffff                                   # samples a chunk consumes / needs
+    RATE, RESAMPLE_ITEM_WORDS = 16000, 4                                               # the model's rate; lh_resample_item_t
 
     def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0, compact: bool = False,
-                 row_buckets=None, pace: bool = False, packets: bool = False, fifo_samples: int = 2048, pcm16: bool = False):
+                 row_buckets=None, pace: bool = False, packets: bool = False, fifo_samples: int = 2048, pcm16: bool = False,
+                 client_rate: int = 16000):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
+        if client_rate != self.RATE:
+            if not packets:
+                raise ValueError("client_rate is the sample rate of a packet streamer's clients: packets=True")
+            if int(client_rate) != client_rate or client_rate % 125 or not 1000 <= client_rate <= 384000:
+                raise ValueError(f"client_rate must be a multiple of 125 Hz in [1000, 384000] — a 128-sample chunk at 16 kHz is "
+                                 f"then a whole number of client samples (8000, 24000, 32000, 48000 ...); {client_rate} is not "
+                                 "(44100 is not either): resample such a stream with resample.Resampler first")
         if packets and not pace:
             raise ValueError("packets are the input of a paced streamer (the device decides who is present): pace=True")
         if pcm16 and not packets:
@@ -1501,8 +1530,33 @@ class SessionStreamer:
             self._item_words = (self.FEED_ITEM_WORDS * S + 3) // 4 * 4
             self._stage = torch.zeros(self._item_words + S * net.num_ch * R // (2 if pcm16 else 1), dtype=torch.int32, device=dev)
             self.last_present = (False,) * S
-            if pcm16:
+            if pcm16 and client_rate == self.RATE:
                 self.out16 = torch.zeros(S, net.n_srcs, net.stft_chunk_size, dtype=torch.int16, device=dev)
+        self.client_rate, self.hop_client, self._resampling = int(client_rate), self.HOP, client_rate != self.RATE
+        if self._resampling:
+            from .resample import resample_bank
+            bank_in, self._w_in, self._o_in, self._n_in = resample_bank(self.client_rate, self.RATE)
+            bank_out, self._w_out, self._o_out, self._n_out = resample_bank(self.RATE, self.client_rate)
+            self._k_in = 2 * self._w_in + self._o_in
+            self.hop_client = self.HOP * self._o_in // self._n_in
+            self.lookahead_in = self._w_in + self._o_in - 1                  # client samples behind a block's first one
+            self.delay_out = (self._w_out + 2 * self._o_out - 1) // self._o_out * self._o_out       # 16 kHz samples, D o
+            # a full FIFO's worth of input plus one block's taps: what `push` can leave unconsumed
+            self.raw_samples = 256
+            while self.raw_samples < self.fifo_samples * self._o_in // self._n_in + self._k_in:
+                self.raw_samples *= 2
+            Rin = self.raw_samples
+            self._raw = torch.zeros(S, net.num_ch, Rin, device=dev)          # a ring per slot and channel, at the client rate
+            self._raw_words = torch.zeros(2, S, dtype=torch.int32, device=dev)       # its wr | rd (rd: only FLUSH writes it)
+            self._tap0 = -self._w_in & self.COUNTER_MASK                     # a stream's first tap: the left pad lies below 0
+            self._raw_wr, self._tap = [0] * S, [self._tap0] * S              # mirrors: raw samples pushed | next block's first tap
+            self._tail = torch.zeros(S, net.n_srcs, self._w_out + self.delay_out, device=dev)
+            self.out_client = torch.zeros(S, net.n_srcs, self.hop_client, dtype=torch.int16 if pcm16 else torch.float32,
+                                          device=dev)
+            self._bank_in, self._bank_out = bank_in.to(dev), bank_out.to(dev)
+            self._ritem_off = self.FEED_ITEM_WORDS * S                       # the resample items follow the feed items
+            self._item_words = ((self.FEED_ITEM_WORDS + self.RESAMPLE_ITEM_WORDS) * S + 3) // 4 * 4
+            self._stage = torch.zeros(self._item_words + S * net.num_ch * Rin // (2 if pcm16 else 1), dtype=torch.int32, device=dev)
         self._gen = [0] * S                                 # generation of the slot's current opening, 0 = idle
         self._next_gen = 1
         self._pending = {}                                  # slot -> command word for the next step
@@ -1604,7 +1658,11 @@ class SessionStreamer:
             else:
                 lib.call("lh_session_end_paced", A(end), len(end), A(carry), len(carry) // 2, P(self.chunk_in), P(st.out), cmd,
                          active, P(self._fault), hold, S, stream)
-            if self.pcm16:
+            if self._resampling:                            # the rows at the client's rate, fp32 or 16-bit
+                lib.call("lh_session_resample_out", P(self.out), P(self._tail), hold, P(self.out_client),
+                         self.FEED_S16 if self.pcm16 else self.FEED_F32, S, P(self._bank_out), self._o_out, self._n_out,
+                         self._w_out, stream)
+            elif self.pcm16:
                 lib.call("lh_session_emit_s16", P(self.out), P(self.out16), S, stream)
 
     def reset(self):
@@ -1619,6 +1677,10 @@ class SessionStreamer:
             self._wr, self._rd = [0] * self.S, [0] * self.S
             self._flush.clear()
             self.last_present = (False,) * self.S
+        if self._resampling:
+            for t in (self._raw, self._raw_words, self._tail, self.out_client):
+                t.zero_()
+            self._raw_wr, self._tap = [0] * self.S, [self._tap0] * self.S
         if self.compact:
             self._tables.zero_()
             self._tables[1:3].fill_(-1)
@@ -2003,16 +2065,35 @@ class SessionStreamer:
         """packets {slot: CPU tensor [2, n]}, float32 (int16 in a `pcm16` streamer), any n >= 0: the clients' contiguous PCM
         as it arrived since the last call.  One fresh pinned buffer (item table, then the samples), one asynchronous copy
         and one `lh_session_feed` launch, whatever the number of packets; never waits for the device.  BufferError, before
-        anything is enqueued or changed for any slot, when a slot would hold more than `fifo_samples`."""
+        anything is enqueued or changed for any slot, when a slot would hold more than `fifo_samples`.
+        A `client_rate` streamer takes the samples at the client's rate: they go to the slot's raw ring, and a second launch
+        (`lh_session_resample_in`) makes the 16 kHz blocks whose taps are now complete — `fifo_samples` bounds those."""
         self._packet_streamer()
         S, R, M, dtype = self.S, self.fifo_samples, self.COUNTER_MASK, torch.int16 if self.pcm16 else torch.float32
         nch, wr, rd, flushed = self.chunk_in.shape[1], self._wr, self._rd, self._flush
+        resamp, blocks = self._resampling, {}
+        if resamp:                                          # the feed serves the raw ring; wr16 / rd stay the FIFO's
+            wr16, wr, tap = self._wr, self._raw_wr, self._tap
+            o, nn, K = self._o_in, self._n_in, self._k_in
         todo = []
         for slot, x in packets.items():
             slot = self._slot(int(slot))
             if not isinstance(x, torch.Tensor) or x.is_cuda or x.dtype != dtype or x.dim() != 2 or x.shape[0] != nch:
                 raise ValueError(f"slot {slot}: a packet is a CPU {dtype} tensor [{nch}, n]")
             n = x.shape[1]
+            if resamp:
+                # the resampler's block arithmetic: a block is made once all K of its samples are there
+                fl = slot in flushed
+                have = 0 if fl else (wr16[slot] - rd[slot]) & M
+                fill = ((0 if fl else wr[slot]) + n - (self._tap0 if fl else tap[slot])) & M
+                nb = 0 if fill < K else (fill - K) // o + 1
+                if have + nb * nn > R:
+                    raise BufferError(f"slot {slot}: {have} samples buffered + {nb * nn} made of the {n} pushed > fifo_samples = "
+                                      f"{R} (at 16 kHz): step() first (while ss.ready(): ss.step()), or flush(slot)")
+                blocks[slot] = nb
+                if n or fl:
+                    todo.append((slot, x, n))
+                continue
             have = 0 if slot in flushed else (wr[slot] - rd[slot]) & M
             if have + n > R:
                 raise BufferError(f"slot {slot}: {have} samples buffered + {n} pushed > fifo_samples = {R}: "
@@ -2031,24 +2112,40 @@ class SessionStreamer:
         buf = src.numpy()
         table = buf[:self.FEED_ITEM_WORDS * len(todo)].reshape(-1, self.FEED_ITEM_WORDS)
         samples = buf[self._item_words:].view(np.int16 if self.pcm16 else np.float32)
-        off = 0
+        i32 = lambda v: v - (1 << 32) if v >> 31 else v       # a 32-bit pattern as an int32 table holds it
+        off, ritems = 0, []
         for i, (slot, x, n) in enumerate(todo):
             flush = slot in flushed
             if flush:
                 wr[slot] = rd[slot] = 0
+                if resamp:                                  # the stream restarts from silence: zero history, phase 0
+                    wr16[slot], tap[slot] = 0, self._tap0
+                    for t in (self._raw[slot], self._tail[slot], self._fifo_words[:, slot]):
+                        t.zero_()
             at = wr[slot]
-            table[i] = (slot, off, n, at - (1 << 32) if at >> 31 else at, self.FEED_FLUSH if flush else 0)
+            table[i] = (slot, off, n, i32(at), self.FEED_FLUSH if flush else 0)
             if n:
                 samples[off:off + nch * n].reshape(nch, n)[...] = x.numpy()
             wr[slot] = (at + n) & M
             off += nch * n
+            nb = blocks.get(slot, 0)
+            if nb:
+                ritems.append((slot, nb, i32(wr16[slot]), i32(tap[slot])))
+                wr16[slot], tap[slot] = (wr16[slot] + nb * nn) & M, (tap[slot] + nb * o) & M
         flushed.clear()
+        if ritems:
+            buf[self._ritem_off:self._ritem_off + self.RESAMPLE_ITEM_WORDS * len(ritems)].reshape(-1, self.RESAMPLE_ITEM_WORDS)[...] = ritems
         self._stage[:used].copy_(src, non_blocking=True)
+        ring, words, Rr = (self._raw, self._raw_words, self.raw_samples) if resamp else (self._fifo, self._fifo_words, R)
         with torch.no_grad(), net._device_ctx(st.chunk):
-            net._lib(st.chunk).call("lh_session_feed", self._stage[self._item_words:].data_ptr(), total * (4 // per),
-                                    self.FEED_S16 if self.pcm16 else self.FEED_F32, self._stage.data_ptr(), len(todo),
-                                    self._fifo.data_ptr(), self._fifo_words[0].data_ptr(), self._fifo_words[1].data_ptr(), R, S,
-                                    net._stream(self.device))
+            lib, stream = net._lib(st.chunk), net._stream(self.device)
+            lib.call("lh_session_feed", self._stage[self._item_words:].data_ptr(), total * (4 // per),
+                     self.FEED_S16 if self.pcm16 else self.FEED_F32, self._stage.data_ptr(), len(todo), ring.data_ptr(),
+                     words[0].data_ptr(), words[1].data_ptr(), Rr, S, stream)
+            if ritems:
+                lib.call("lh_session_resample_in", ring.data_ptr(), Rr, self._stage[self._ritem_off:].data_ptr(), len(ritems),
+                         self._fifo.data_ptr(), self._fifo_words[0].data_ptr(), R, S, self._bank_in.data_ptr(), o, nn,
+                         self._w_in, stream)
 
     def set_embedding(self, slot: int, embed: torch.Tensor):
         """Re-target an open slot ("look once" at another speaker): the carried state is kept."""
@@ -2162,4 +2259,6 @@ class SessionStreamer:
             else:
                 self.graphs[st.parity].replay()
         st.parity ^= 1
+        if self._resampling:
+            return self.out_client
         return self.out16 if self.pcm16 else self.out

@@ -41,6 +41,11 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         pinned host memory; (b) everyone present.  The loop waits for every step, so the host's time inside `push` is in the
         interval; the `pipelined` arm enqueues the push for step i + 1 behind step i instead, as a host does that takes
         packets while the chunk runs.  `scatter` is the spread of the paced blocks' p50.
+    python scripts/bench_sessions.py --client-rate 48000 [--batches 1,64] [--out profiles/client_rate_cost.txt]
+        what resampling on the device costs a packet streamer, in DEVICE time per step, push included as above: everyone
+        present, a chunk's worth of client samples per slot and step (384 at 48 kHz) against the 16 kHz packet streamer fed 128,
+        blocks of the two interleaved in one run; `scatter` is the spread of the 16 kHz blocks' p50.  Then the offline
+        `Resampler(client_rate, 16000)` on [64, 240000]: bytes read and written over the p50 time against the 8 TB/s of HBM.
 """
 import argparse
 import json
@@ -465,6 +470,89 @@ def packets_bench(net, args):
             f.write(text + "\n")
 
 
+def client_rate_bench(net, args):
+    from lookoncetohear_amd.resample import Resampler
+    rate, reps, N, HBM = args.client_rate, 4, 80000, 8.0e12
+    hop = 128 * rate // 16000
+    lines = [f"client rate {rate} Hz, device time per step (HIP events around push + step), everyone present, {args.steps} steps per "
+             f"figure in {reps} interleaved blocks after {args.warmup} warm-up; the yardstick is the 16 kHz packet streamer of the "
+             f"same run"]
+    for B in [int(b) for b in args.batches.split(",")]:
+        d = synth.batch(list(range(B)), N)
+        host16 = d["mixture"].pin_memory()
+        # the same signal read at the client's rate: what is timed does not depend on the samples
+        host_c = synth.batch(list(range(B)), N * rate // 16000)["mixture"].pin_memory() if rate != 16000 else host16
+        emb = d["embedding_gt"][:, 0].to(DEV)
+        base = net.make_session_streamer(B, DEV, pace=True, packets=True)
+        cli = net.make_session_streamer(B, DEV, pace=True, packets=True, client_rate=rate)
+        for ss in (base, cli):
+            for s in range(B):
+                ss.open(s, emb[s])
+
+        def run(ss, host, per, n, pos):
+            ms = []
+            total = host.shape[-1]
+            for _ in range(n):
+                at = pos[0]
+                packets = {s: host[s, :, at:at + per].contiguous() for s in range(B)}
+                pos[0] = (at + per) % (total - per)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ss.push(packets)
+                ss.step()
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            return ms
+
+        pos16, posc = [0], [0]
+        base.push({s: host16[s, :, :64] for s in range(B)})                  # the look-ahead, once
+        cli.push({s: host_c[s, :, :64 * rate // 16000 + cli.lookahead_in] for s in range(B)})
+        run(base, host16, 128, args.warmup, pos16), run(cli, host_c, hop, args.warmup, posc)
+        assert all(base.last_present) and all(cli.last_present)
+        ms, p50s = {"16 kHz": [], "client": []}, []
+        for rep in range(reps):
+            n = args.steps // reps
+            blk = run(base, host16, 128, n, pos16)
+            ms["16 kHz"] += blk
+            p50s.append(pct(blk, 0.5))
+            ms["client"] += run(cli, host_c, hop, n, posc)
+            assert all(base.last_present) and all(cli.last_present)
+        torch.cuda.synchronize()
+        assert base.faults() == [] and cli.faults() == [] and len(cli.active) == B
+        r = {k: stats(v) for k, v in ms.items()}
+        scatter = max(p50s) - min(p50s)
+        cost = r["client"]["p50_ms"] - r["16 kHz"]["p50_ms"]
+        lines.append(f"S={B:3d}   16 kHz packets: p50 {r['16 kHz']['p50_ms']:.4f} p99 {r['16 kHz']['p99_ms']:.4f} ms   client rate {rate}: "
+                     f"p50 {r['client']['p50_ms']:.4f} p99 {r['client']['p99_ms']:.4f} ms   difference {1e3 * cost:+.1f} us "
+                     f"({100.0 * cost / r['16 kHz']['p50_ms']:+.1f} %), scatter of the 16 kHz blocks {1e3 * scatter:.1f} us: "
+                     f"{'WITHIN' if abs(cost) <= 3 * scatter else 'NOT within'} three times the scatter")
+        del base, cli
+    rows, n_in = 64, 240000
+    rs = Resampler(rate, 16000)
+    x = torch.randn(rows, n_in, device=DEV)
+    for _ in range(10):
+        y = rs(x)
+    ms = []
+    for _ in range(50):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        y = rs(x)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    moved = 4 * (x.numel() + y.numel())
+    p50 = pct(ms, 0.5)
+    lines.append(f"Resampler({rate}, 16000) on [{rows}, {n_in}] -> {list(y.shape)}: p50 {p50:.4f} ms (min {min(ms):.4f}, max {max(ms):.4f}, "
+                 f"50 launches), {moved / 1e6:.1f} MB read + written = {moved / p50 * 1e3 / 1e12:.3f} TB/s = "
+                 f"{moved / p50 * 1e3 / HBM:.3f} of HBM (8 TB/s)")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def suspend_many_bench(net, args):
     from lookoncetohear_amd import _cabi
 
@@ -555,6 +643,7 @@ def main():
     ap.add_argument("--suspend", action="store_true")
     ap.add_argument("--suspend-many", action="store_true")
     ap.add_argument("--packets", action="store_true")
+    ap.add_argument("--client-rate", type=int, default=0)
     ap.add_argument("--many", default="1,8,64")
     ap.add_argument("--tiles", default="")
     ap.add_argument("--slots", type=int, default=64)
@@ -583,6 +672,8 @@ def main():
         return suspend_many_bench(net, args)
     if args.packets:
         return packets_bench(net, args)
+    if args.client_rate:
+        return client_rate_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
