@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (23); bumped on any signature change. */
+/* ABI version of this header (24); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -446,6 +446,40 @@ int lh_emb_head(const float* z, const void* w_pk, const float* bias, const float
  */
 int lh_render_binaural(const float* src, const float* rir, const float* gain, const int* tgt_idx, float* events,
                        unsigned* peak, float* mixture, float* target, int B, int S1, int N, int Lh, lh_stream_t stream);
+
+/* Moving sources (ABI 24): lh_render_binaural with impulse responses that change along a path, one point per `frame`
+ * samples.  The INTERFACE follows the reference's binding of its native simulator (src/datasets/motion_simulator.py:30-95:
+ * simulator_set_hrtf -> `bank`, simulator_add_source(audio, path) -> lh_path_nearest, simulator_simulate ->
+ * lh_render_moving); the ARITHMETIC is this project's own definition, stated here — the native library and its source are
+ * absent, so nothing below is a restatement pinned to the reference.
+ * Per utterance b, row s (sources first, the noise bed LAST), ear e, sample n < N:
+ *     f  = n / frame (integer),  w = (float)(n % frame) / (float)frame      (fp32 IEEE division)
+ *     ha = bank[bank_of[b]][idx[b][s][f]][e],  hb = bank[bank_of[b]][idx[b][s][f + 1]][e]
+ *     a  = sum_{k < Lh} ha[k] x[n - k],  b_ = sum_{k < Lh} hb[k] x[n - k]   (x[< 0] = 0; each one fp32 fmaf chain over k
+ *                                                                            ascending from 0.f)
+ *     events[b][s][e][n] = fmaf(w, b_ - a, a) * gain[b][s]
+ * an output-side linear cross-fade between the responses of consecutive path points: the filter belongs to the output
+ * sample.  Where idx[f] == idx[f + 1] the row has the bits of lh_render_binaural's direct form (Lh < 1024 or Lh > 4097) with
+ * that response.  Direct form at every Lh.
+ *   bank     [K][P][2][Lh]    K response banks of P entries (one bank per utterance: the reference picks one SOFA file per scene)
+ *   bank_of  [B] int32        in [0, K)
+ *   idx      [B][S1][F] int32 bank entry per path point, F >= ceil(N / frame) + 1 (extra points are ignored); bank_of and
+ *                             idx are clamped into range where they are read
+ *   everything else as lh_render_binaural; peak, mixture and target keep its exact semantics.
+ * LH_ERR_ARG: null pointer, a dimension <= 0, B * S1 > 65535, F < ceil(N / frame) + 1.  LH_ERR_UNSUPPORTED: frame % 8 != 0.
+ * A refused call writes nothing.  No atomics in the FIR: bit-identical from call to call, and row b does not depend on the
+ * other utterances.
+ *
+ * lh_path_nearest: idx[b][s][t] = the LOWEST j with the largest d_j = fmaf(v.z, p_j.z, fmaf(v.y, p_j.y, v.x * p_j.x)) in
+ * fp32, v = paths[b][s][t], p_j = positions[bank_of[b]][j] (unit vectors: the caller converts SOFA coordinates; the scale
+ * of v does not matter).  A zero vector gives 0; a non-finite point gives SOME index in [0, P).
+ *   paths [B][S1][F][3], positions [K][P][3], bank_of [B] in [0, K), idx [B][S1][F] out
+ * LH_ERR_ARG: null pointer, a dimension <= 0, B * S1 > 65535. */
+int lh_path_nearest(const float* paths, const float* positions, const int* bank_of, int* idx, int B, int S1, int F, int P, int K,
+                    lh_stream_t stream);
+int lh_render_moving(const float* src, const float* bank, const int* bank_of, const int* idx, const float* gain,
+                     const int* tgt_idx, float* events, unsigned* peak, float* mixture, float* target, int B, int S1, int N,
+                     int Lh, int P, int K, int F, int frame, lh_stream_t stream);
 
 /* Eval metrics on the device (reference src/ts_hear_test.py:139-146, torchmetrics SI-SNR restated): per utterance
  * output_sisnr, si_snr_i (both averaged over the 2 channels) and cosine(embedding, embedding_gt); fp64 moments.

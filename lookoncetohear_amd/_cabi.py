@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -85,6 +85,9 @@ SIGNATURES = {
     "lh_emb_attn_block": [_P] * 24 + [_I, _I, _P],
     "lh_emb_head": [_P] * 7 + [_I, _I, _P],
     "lh_render_binaural": [_P] * 8 + [_I, _I, _I, _I, _P],
+    # moving sources (ABI 24): bank lookup of a path and the time-varying FIR, BinauralRenderer.nearest / render_moving
+    "lh_path_nearest": [_P] * 4 + [_I] * 5 + [_P],
+    "lh_render_moving": [_P] * 10 + [_I] * 8 + [_P],
     "lh_metric_sums": [_P] * 8 + [_I, _I, _I, _P],
     "lh_binaural_cues": [_P] * 5 + [_I, _I, _I, _I, c_double, _P],
     "lh_range_status": [_P, _P],

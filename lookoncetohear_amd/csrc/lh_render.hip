@@ -10,6 +10,7 @@
 //                  78 TFLOP/s as the vector unit.  Each thread owns 8 consecutive outputs and keeps a sliding
 //                  15-sample window of x in registers: 8 LDS reads and 8 scalar filter taps feed 64 FMAs.
 //   k_fft_conv     the same convolution by overlap-save FFT for 1024 <= Lh <= 4097 taps (BRIR-length responses)
+//   k_fir_moving   moving sources: two such chains per output, cross-faded between consecutive path points (lh_render_fft.hip)
 //   k_mix_peak     peak of |sum of sources| per utterance (order-independent: atomicMax on the float bit pattern)
 //   k_mix_apply    events / norm (when norm > 1), mixture = ((e0 + e1) + e2) + noise in the reference's order, target
 //   k_resample     polyphase sinc resampling of whole rows (the reference's last dataset step, torchaudio Resample, and its
@@ -105,6 +106,10 @@ constexpr int FC_LOG = 13, FC_F = 1 << FC_LOG;    // transform size
 constexpr int FC_L = FC_F / 2;                    // outputs per block (Lh - 1 <= FC_F - FC_L)
 constexpr int FC_LH_MIN = 1024, FC_LH_MAX = FC_F - FC_L + 1;
 int launch_fft_conv(const float* x, const float* h, const float* gain, float* y, int N, int Lh, int rows, hipStream_t st);
+// Moving sources (k_fir_moving, a time-varying FIR; the project's own definition) live there too: a second FIR in this file
+// would spend the library's packed-fp32 budget (tests/test_cabi_symbols.py) twice.
+int launch_fir_moving(const float* x, const float* bank, const int* bank_of, const int* idx, const float* gain, float* y,
+                      int rows, int S1, int N, int Lh, int P, int K, int F, int frame, hipStream_t st);
 
 // sum of the S1 rendered sources in the reference's order: ((e0 + e1) + ...) + noise (the last row)
 __device__ __forceinline__ float mix_sum(const float* __restrict__ ev, long stride, int S1, long i, float inv, bool scale) {
@@ -221,6 +226,28 @@ extern "C" int lh_render_binaural(const float* src, const float* rir, const floa
         hipLaunchKernelGGL(k_fir_causal, dim3((N + FIR_TILE - 1) / FIR_TILE, B * S1 * 2), dim3(256), 0, st, src, rir, gain,
                            events, N, Lh);
     }
+    const int chunks = (int)((2L * N + 256 * 8 - 1) / (256 * 8));
+    hipLaunchKernelGGL(k_mix_peak, dim3(chunks, B), dim3(256), 0, st, events, peak, S1, N);
+    hipLaunchKernelGGL(k_mix_apply, dim3(chunks, B), dim3(256), 0, st, events, peak, tgt_idx, mixture, target, S1, N);
+    return check_launch();
+}
+
+// lh_render_binaural for moving sources: row s of utterance b is rendered through bank[bank_of[b]][idx[b][s][f]] and
+// [f + 1], cross-faded over frame f (k_fir_moving in lh_render_fft.hip has the definition); peak, mixture and target are
+// lh_render_binaural's own kernels.  A refused call writes nothing.
+extern "C" int lh_render_moving(const float* src, const float* bank, const int* bank_of, const int* idx, const float* gain,
+                                const int* tgt_idx, float* events, unsigned* peak, float* mixture, float* target, int B, int S1,
+                                int N, int Lh, int P, int K, int F, int frame, lh_stream_t stream) {
+    using namespace lh;
+    if (!src || !bank || !bank_of || !idx || !gain || !tgt_idx || !events || !peak || !mixture || !target || B <= 0 || S1 <= 0 ||
+        N <= 0 || Lh <= 0 || P <= 0 || K <= 0 || F <= 0 || frame <= 0 || (long)B * S1 > 65535)
+        return LH_ERR_ARG;
+    if (frame % 8) return LH_ERR_UNSUPPORTED;                 // a thread's 8 consecutive outputs must not straddle a frame
+    if ((long)F < ((long)N + frame - 1) / frame + 1) return LH_ERR_ARG;      // frame f blends path points f and f + 1
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(peak, 0, sizeof(unsigned) * B, st) != hipSuccess) return LH_ERR_LAUNCH;
+    if (launch_fir_moving(src, bank, bank_of, idx, gain, events, B * S1, S1, N, Lh, P, K, F, frame, st) != LH_OK)
+        return LH_ERR_LAUNCH;
     const int chunks = (int)((2L * N + 256 * 8 - 1) / (256 * 8));
     hipLaunchKernelGGL(k_mix_peak, dim3(chunks, B), dim3(256), 0, st, events, peak, S1, N);
     hipLaunchKernelGGL(k_mix_apply, dim3(chunks, B), dim3(256), 0, st, events, peak, tgt_idx, mixture, target, S1, N);

@@ -3,6 +3,7 @@
 // vectorisers.  Its complex multiplies become v_pk_mul_f32 / v_pk_fma_f32 with op_sel:[0,1] (src1's halves crossed)
 // under SLP — the one packed-fp32 form that returns wrong lanes 48..63 next to matrix-heavy kernels on this chip
 // (profiles/r03c_packed_fp32_corruption.txt, lookoncetohear_amd/build.py).
+// Below it: the moving-source renderer's two kernels, k_fir_moving and k_path_nearest (lh_render_moving, lh_path_nearest).
 #include "lh_common.h"
 
 namespace lh {
@@ -108,4 +109,200 @@ int launch_fft_conv(const float* x, const float* h, const float* gain, float* y,
     return check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Moving sources: a time-varying FIR (include/lookonce_hip.h, lh_render_moving).  The arithmetic is the project's OWN
+// definition — the reference renders its moving scenes with a native library (`moving_sources.so`, bound by
+// src/datasets/motion_simulator.py:30-95) whose source is absent, so nothing here is pinned to it; only the interface
+// (one response bank per scene, a path point per frame, add_source / simulate) follows that binding.
+//
+//   f = n / frame,  w = (float)(n % frame) / (float)frame,  ha = bank[idx[f]][ear],  hb = bank[idx[f + 1]][ear]
+//   a = sum_k ha[k] x[n - k],  b = sum_k hb[k] x[n - k]   (each ONE fp32 fmaf chain over k ascending from 0.f: k_fir_causal's)
+//   y[n] = fmaf(w, b - a, a) * gain
+//
+// an output-side cross-fade between the responses of consecutive path points.  It lives in this file, not next to
+// k_fir_causal, because this one is compiled without the vectorisers: the library's packed-fp32 budget
+// (tests/test_cabi_symbols.py) is spent on the static FIR.
+//
+// k_fir_moving: one wave = one ear of one segment (at most 512 outputs, 8 per lane) of ONE frame, so both tap sets are
+// wave-uniform and load as scalars; frame % 8 == 0 keeps a lane's 8 outputs inside the frame.  A workgroup is four
+// waves: two consecutive segments x two ears of one row.  The span of x they need is staged in LDS in stages of MV_KT
+// taps (k_fir_causal's padded layout and register sliding window); every staged sample feeds both ears and both chains:
+// 8 LDS reads per 128 FMAs.  A frame whose two path points name the same bank entry runs one chain (b - a would be
+// exactly 0): a wave-uniform branch, same bits for finite input.  No atomics; every output is written by one lane.
+// ------------------------------------------------------------------------------------------------------
+constexpr int MV_R = 8;                          // outputs per lane
+constexpr int MV_SEG = 64 * MV_R;                // outputs per wave at most: 512
+constexpr int MV_OUT = 2 * MV_SEG;               // output extent of a workgroup's two segments: at most 1024
+constexpr int MV_KT = 1024;                      // taps per LDS stage (multiple of 2 MV_R)
+constexpr int MV_SPAN = MV_OUT + MV_KT + MV_R;   // samples staged per stage
+
+// `TWO`: hb differs from ha.  One stage: taps k0 .. k0 + kend of the chains of this lane's 8 outputs, whose first one sits
+// u * 8 samples into the workgroup's extent.
+template <bool TWO>
+__device__ __forceinline__ void mv_stage(const float* __restrict__ xs, const float* __restrict__ ha, const float* __restrict__ hb,
+                                         float (&acc_a)[MV_R], float (&acc_b)[MV_R], int u, int k0, int kend, int Lh) {
+    float wa[MV_R], wb[MV_R];
+    {
+        const float* wp = xs + 9 * (u + MV_KT / 8 + 1);
+#pragma unroll
+        for (int j = 0; j < MV_R - 1; ++j) wb[j] = wp[j];
+        wb[MV_R - 1] = 0.f;
+    }
+    auto chunk = [&](float (&lo)[MV_R], const float (&hi)[MV_R], int k) {
+        const float* wp = xs + 9 * (u + (MV_KT - k) / 8);
+#pragma unroll
+        for (int j = 0; j < MV_R; ++j) lo[j] = wp[j];
+        const int kt0 = k0 + k;
+        float ka[MV_R], kb[MV_R];
+        if (kt0 + MV_R <= Lh) {                                    // wave-uniform: 32-byte scalar loads
+#pragma unroll
+            for (int kk = 0; kk < MV_R; ++kk) {
+                ka[kk] = ha[kt0 + kk];
+                kb[kk] = TWO ? hb[kt0 + kk] : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < MV_R; ++kk) {
+                ka[kk] = kt0 + kk < Lh ? ha[kt0 + kk] : 0.f;
+                kb[kk] = TWO && kt0 + kk < Lh ? hb[kt0 + kk] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < MV_R; ++kk)
+#pragma unroll
+            for (int r = 0; r < MV_R; ++r) {
+                const int i = MV_R - 1 + r - kk;                   // compile-time after unrolling
+                const float xv = i >= MV_R ? hi[i - MV_R] : lo[i];
+                acc_a[r] = fmaf(ka[kk], xv, acc_a[r]);
+                if (TWO) acc_b[r] = fmaf(kb[kk], xv, acc_b[r]);
+            }
+    };
+    for (int k = 0; k < kend; k += 2 * MV_R) {
+        chunk(wa, wb, k);
+        if (k + MV_R < kend) chunk(wb, wa, k + MV_R);
+    }
+}
+
+// grid (ceil(segments / 2), B * S1), segments = ceil(N / frame) * spf, spf = ceil(frame / MV_SEG)
+// x [B*S1][N], bank [K][P][2][Lh], bank_of [B], idx [B*S1][F], gain [B*S1], y [B*S1][2][N]
+__global__ void __launch_bounds__(256) k_fir_moving(const float* __restrict__ x, const float* __restrict__ bank,
+                                                    const int* __restrict__ bank_of, const int* __restrict__ idx,
+                                                    const float* __restrict__ gain, float* __restrict__ y, int S1, int N, int Lh,
+                                                    int P, int K, int F, int frame, int spf) {
+    __shared__ float xs[MV_SPAN + MV_SPAN / 8 + 8];
+    const int tid = threadIdx.x, lane = tid & 63, w = wave_id(tid);
+    const int row = blockIdx.y, ear = w & 1;
+    // the workgroup's two segments; a segment is part j of frame f: outputs [f frame + j MV_SEG, ... + cnt)
+    const int sg0 = blockIdx.x * 2, sg = sg0 + (w >> 1);
+    const int n_lo = (sg0 / spf) * frame + (sg0 % spf) * MV_SEG;         // first output of the workgroup (a multiple of 8)
+    const int f = sg / spf, j = sg - f * spf;
+    const long nw = (long)f * frame + (long)j * MV_SEG;                  // the wave's first output: in [n_lo, n_lo + MV_SEG]
+    const int cnt = nw < N ? min(min(MV_SEG, frame - j * MV_SEG), (int)(N - nw)) : 0;      // 0: a wave with nothing to do
+    const int u = (cnt ? (int)(nw - n_lo) / MV_R : 0) + lane;            // < 128
+    // clamped when read: no argument of the C ABI can make the kernel read outside the bank
+    const int bk = min(max(bank_of[row / S1], 0), K - 1);
+    const int fa = min(f, F - 2);                                        // (f <= F - 2 for every wave with cnt > 0)
+    const int ia = min(max(idx[(long)row * F + fa], 0), P - 1), ib = min(max(idx[(long)row * F + fa + 1], 0), P - 1);
+    const float* ha = bank + (((long)bk * P + ia) * 2 + ear) * Lh;
+    const float* hb = bank + (((long)bk * P + ib) * 2 + ear) * Lh;
+    const bool two = ia != ib;
+    const float* xc = x + (long)row * N;
+    float acc_a[MV_R], acc_b[MV_R];
+#pragma unroll
+    for (int r = 0; r < MV_R; ++r) acc_a[r] = acc_b[r] = 0.f;
+    // taps beyond the last output only ever meet x[<0] = 0: skip them (per workgroup for the barriers, per wave for the work)
+    const int lh_wg = (int)min((long)Lh, (long)n_lo + MV_OUT), lh_w = cnt ? (int)min((long)Lh, nw + cnt) : 0;
+    for (int k0 = 0; k0 < lh_wg; k0 += MV_KT) {
+        // staged sample i holds x[lo + i], lo = n_lo - k0 - MV_KT - MV_R + 1 (zeros outside [0, N)); this stage's taps reach
+        // back to i = MV_KT - (its tap count, rounded up to 8)
+        const long lo = (long)n_lo - k0 - MV_KT - MV_R + 1;
+        const int i0 = MV_KT - ((min(MV_KT, lh_wg - k0) + MV_R - 1) & ~(MV_R - 1));
+        __syncthreads();
+        for (int i = i0 + tid; i < MV_SPAN; i += 256) {
+            const long p = lo + i;
+            xs[i + (i >> 3)] = (p >= 0 && p < N) ? xc[p] : 0.f;
+        }
+        __syncthreads();
+        const int kend = min(MV_KT, lh_w - k0);                          // <= 0: nothing for this wave in this stage
+        if (two) mv_stage<true>(xs, ha, hb, acc_a, acc_b, u, k0, kend, Lh);
+        else mv_stage<false>(xs, ha, hb, acc_a, acc_b, u, k0, kend, Lh);
+    }
+    if (lane * MV_R >= cnt) return;
+    const float g = gain[row];
+    const int m0 = j * MV_SEG + lane * MV_R;                             // position in the frame of the lane's first output
+    const float fr = (float)frame;
+    float out[MV_R];
+#pragma unroll
+    for (int r = 0; r < MV_R; ++r) {
+        const float a = acc_a[r];
+        out[r] = (two ? fmaf((float)(m0 + r) / fr, acc_b[r] - a, a) : a) * g;
+    }
+    float* yc = y + ((long)row * 2 + ear) * N;
+    const long n = nw + lane * MV_R;
+    if (n + MV_R <= N && ((N & 3) == 0)) {
+        *reinterpret_cast<float4*>(&yc[n]) = make_float4(out[0], out[1], out[2], out[3]);
+        *reinterpret_cast<float4*>(&yc[n + 4]) = make_float4(out[4], out[5], out[6], out[7]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < MV_R; ++r)
+            if (n + r < N) yc[n + r] = out[r];
+    }
+}
+
+int launch_fir_moving(const float* x, const float* bank, const int* bank_of, const int* idx, const float* gain, float* y,
+                      int rows, int S1, int N, int Lh, int P, int K, int F, int frame, hipStream_t st) {
+    const int spf = (frame + MV_SEG - 1) / MV_SEG;
+    const long segs = ((long)N + frame - 1) / frame * spf;               // <= N / 8 + spf
+    hipLaunchKernelGGL(k_fir_moving, dim3((unsigned)((segs + 1) / 2), rows), dim3(256), 0, st, x, bank, bank_of, idx, gain, y, S1,
+                       N, Lh, P, K, F, frame, spf);
+    return check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------
+// k_path_nearest: the bank lookup of the binding's `simulator_add_source(audio, path)` — for every path point v the bank
+// position (unit vectors; the scale of v does not matter) with the largest d_j = fmaf(v.z, p.z, fmaf(v.y, p.y, v.x p.x)),
+// the LOWEST such j (a strict > while scanning upward).  A zero vector gives 0; a non-finite point some index in [0, P).
+// Not hot (about 26 k points x 1250 positions per batch): one thread per point, the positions through LDS in tiles.
+// grid (ceil(F / 256), B * S1)
+// ------------------------------------------------------------------------------------------------------
+constexpr int PN_TILE = 1024;
+__global__ void __launch_bounds__(256) k_path_nearest(const float* __restrict__ paths, const float* __restrict__ positions,
+                                                      const int* __restrict__ bank_of, int* __restrict__ idx, int S1, int F, int P,
+                                                      int K) {
+    __shared__ float ps[PN_TILE * 3];
+    const int tid = threadIdx.x, row = blockIdx.y, t = blockIdx.x * 256 + tid;
+    const int bk = min(max(bank_of[row / S1], 0), K - 1);
+    const float* pos = positions + (long)bk * P * 3;
+    float vx = 0.f, vy = 0.f, vz = 0.f;
+    if (t < F) {
+        const float* v = paths + ((long)row * F + t) * 3;
+        vx = v[0], vy = v[1], vz = v[2];
+    }
+    float best = 0.f;
+    int arg = 0;
+    for (int p0 = 0; p0 < P; p0 += PN_TILE) {
+        const int np = min(PN_TILE, P - p0);
+        __syncthreads();
+        for (int i = tid; i < np * 3; i += 256) ps[i] = pos[(long)p0 * 3 + i];
+        __syncthreads();
+        for (int q = 0; q < np; ++q) {
+            const float d = fmaf(vz, ps[3 * q + 2], fmaf(vy, ps[3 * q + 1], vx * ps[3 * q]));
+            if (p0 + q == 0) best = d;
+            else if (d > best) best = d, arg = p0 + q;
+        }
+    }
+    if (t < F) idx[(long)row * F + t] = arg;
+}
+
 }  // namespace lh
+
+// Bank lookup for lh_render_moving (include/lookonce_hip.h).
+extern "C" int lh_path_nearest(const float* paths, const float* positions, const int* bank_of, int* idx, int B, int S1, int F,
+                               int P, int K, lh_stream_t stream) {
+    using namespace lh;
+    if (!paths || !positions || !bank_of || !idx || B <= 0 || S1 <= 0 || F <= 0 || P <= 0 || K <= 0 || (long)B * S1 > 65535)
+        return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_path_nearest, dim3((F + 255) / 256, B * S1), dim3(256), 0, (hipStream_t)stream, paths, positions, bank_of,
+                       idx, S1, F, P, K);
+    return check_launch();
+}

@@ -52,3 +52,65 @@ class BinauralRenderer(_cabi.HipHost):
             lib.call("lh_render_binaural", P(srcs), P(rirs), P(gains), P(tgt_idx), P(events), P(peak), P(mixture),
                      P(target), B, S1, N, Lh, st)
         return mixture, target, peak.view(torch.float32), events
+
+    # ---- moving sources (ABI 24).  The interface follows the reference's binding of its native simulator
+    # (src/datasets/motion_simulator.py: set_hrtf -> `bank`, add_source(audio, path) -> `nearest`, simulate ->
+    # `render_moving`); the arithmetic is this project's own definition (include/lookonce_hip.h), the native code is absent.
+    def nearest(self, paths: torch.Tensor, positions: torch.Tensor, bank_of: torch.Tensor) -> torch.Tensor:
+        """paths [B, S1, F, 3] (one point per frame, any scale), positions [K, P, 3] (unit vectors), bank_of [B] ->
+        idx [B, S1, F] int32: per point the bank entry with the largest dot product, the lowest index among equals."""
+        lib = self._lib(paths)
+        if paths.dim() != 4 or paths.shape[3] != 3 or positions.dim() != 3 or positions.shape[2] != 3:
+            raise ValueError(f"expected paths [B,S1,F,3] and positions [K,P,3]; got {tuple(paths.shape)} and {tuple(positions.shape)}")
+        B, S1, F, _ = paths.shape
+        K, P, _ = positions.shape
+        if tuple(bank_of.shape) != (B,):
+            raise ValueError("bank_of must be [B]")
+        if int(bank_of.max()) >= K or int(bank_of.min()) < 0:
+            raise IndexError("bank_of out of range")
+        dev = paths.device
+        paths, positions = paths.contiguous().float(), positions.contiguous().float()
+        bank_of = bank_of.to(torch.int32).contiguous()
+        idx = torch.empty(B, S1, F, dtype=torch.int32, device=dev)
+        D = lambda t: t.data_ptr()
+        with self._device_ctx(paths):
+            lib.call("lh_path_nearest", D(paths), D(positions), D(bank_of), D(idx), B, S1, F, P, K, self._stream(dev))
+        return idx
+
+    def render_moving(self, srcs: torch.Tensor, bank: torch.Tensor, bank_of: torch.Tensor, idx: torch.Tensor, gains: torch.Tensor,
+                      tgt_idx: torch.Tensor, frame: int = 400) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`render` for sources that move: srcs [B, S1, N] (noise bed LAST), bank [K, P, 2, Lh], bank_of [B], idx [B, S1, F]
+        with F >= ceil(N / frame) + 1 (row s passes through bank entry idx[b, s, f] at sample f * frame and is cross-faded
+        towards idx[b, s, f + 1] over the frame), gains [B, S1], tgt_idx [B] -> mixture [B, 2, N], target [B, 2, N],
+        norm_factor [B], events [B, S1, 2, N].  frame % 8 == 0."""
+        lib = self._lib(srcs)
+        if srcs.dim() != 3 or bank.dim() != 4 or bank.shape[2] != 2:
+            raise ValueError(f"expected srcs [B,S1,N] and bank [K,P,2,Lh]; got {tuple(srcs.shape)} and {tuple(bank.shape)}")
+        B, S1, N = srcs.shape
+        K, P, _, Lh = bank.shape
+        frame = int(frame)
+        if frame <= 0 or frame % 8:
+            raise ValueError(f"frame must be a positive multiple of 8; got {frame}")
+        if idx.dim() != 3 or idx.shape[:2] != srcs.shape[:2] or idx.shape[2] < -(-N // frame) + 1:
+            raise ValueError(f"idx must be [B,S1,F] with F >= ceil(N / frame) + 1 = {-(-N // frame) + 1}; got {tuple(idx.shape)}")
+        if tuple(gains.shape) != (B, S1) or tuple(tgt_idx.shape) != (B,) or tuple(bank_of.shape) != (B,):
+            raise ValueError("gains must be [B,S1], tgt_idx [B] and bank_of [B]")
+        # one host read each, before anything is launched (`render` pays the same for tgt_idx)
+        if int(tgt_idx.max()) >= S1 or int(tgt_idx.min()) < 0:
+            raise IndexError("tgt_idx out of range")
+        if int(bank_of.max()) >= K or int(bank_of.min()) < 0:
+            raise IndexError("bank_of out of range")
+        if int(idx.max()) >= P or int(idx.min()) < 0:
+            raise IndexError("idx out of range")
+        F = idx.shape[2]
+        dev = srcs.device
+        srcs, bank, gains = srcs.contiguous().float(), bank.contiguous().float(), gains.contiguous().float()
+        bank_of, idx, tgt_idx = (t.to(torch.int32).contiguous() for t in (bank_of, idx, tgt_idx))
+        events = torch.empty(B, S1, 2, N, device=dev)
+        mixture, target = torch.empty(B, 2, N, device=dev), torch.empty(B, 2, N, device=dev)
+        peak = torch.empty(B, dtype=torch.int32, device=dev)
+        D = lambda t: t.data_ptr()
+        with self._device_ctx(srcs):
+            lib.call("lh_render_moving", D(srcs), D(bank), D(bank_of), D(idx), D(gains), D(tgt_idx), D(events), D(peak), D(mixture),
+                     D(target), B, S1, N, Lh, P, K, F, frame, self._stream(dev))
+        return mixture, target, peak.view(torch.float32), events
