@@ -259,6 +259,20 @@ int lh_ring_advance_rows(int* pos, const int* write_pos, int modulo, int n_rows,
 int lh_proj_ln_res(const float* merged, const void* w_pk, const float* bias, const float* slope,
                    const float* ln_w, const float* ln_b, const float* y2, const float* gain, float* out, int B,
                    int T, lh_stream_t stream);
+/* Fan-out form (ABI 25): K enrolled speakers per mixture.  The embedding enters the network only here, in front of block 1
+ * (tfgridnet_causal.py:247-251), so the front end and block 0 of a mixture are the same for every one of its targets: the
+ * un-gained frame y2 + LN(PReLU(W m + b)) is computed once and stored K times,
+ *   out[b * K + j] = (y2[b] + LN(PReLU(W m[b] + b))) * gain[b * K + j],   0 <= j < K,
+ * each product the single fp32 multiply of lh_proj_ln_res: row b * K + j has the bits of lh_proj_ln_res with gain[b * K + j].
+ *   merged [B][T][4][97][16], y2 [B][T][97][64] and the weights as above; gain [B*K][97][64]; out [B*K][T][97][64]
+ * lh_proj_ln_res_fan_win: frames [t0, t0 + Tc) of every row, like lh_proj_ln_res_win (time windows, below).
+ * LH_ERR_ARG: a null pointer (gain included), K < 1, a window outside [0, T).  (Net.forward_many, lookoncetohear_amd/net.py) */
+int lh_proj_ln_res_fan(const float* merged, const void* w_pk, const float* bias, const float* slope, const float* ln_w,
+                       const float* ln_b, const float* y2, const float* gain, float* out, int B, int T, int K,
+                       lh_stream_t stream);
+int lh_proj_ln_res_fan_win(const float* merged, const void* w_pk, const float* bias, const float* slope, const float* ln_w,
+                           const float* ln_b, const float* y2, const float* gain, float* out, int B, int T, int t0, int Tc,
+                           int K, lh_stream_t stream);
 
 /* A.4  causal ConvTranspose2d(64->4,3x3) + spectrum re-pack + iSTFT synthesis/overlap-add.
  * Replaces tfgridnet_causal.py:256-273 and the look-ahead trim of net.py:61.

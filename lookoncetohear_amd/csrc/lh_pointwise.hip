@@ -377,12 +377,15 @@ __device__ float lh_dbg_part[8 * 24 * 256 * 4];
 #endif
 // ------------------------------------------------------------------------------------------------------
 // attn_concat_proj + LN over (f,c) + residual (+ speaker gain); persistent, grid-stride over frames
+// FAN (lh_proj_ln_res_fan, ABI 25): `nfan` speaker gains per utterance — gain [B * nfan][97][64], out [B * nfan][T][97][64]; the
+// un-gained frame is computed once and stored nfan times, row b * nfan + j under gain[b * nfan + j]
 // ------------------------------------------------------------------------------------------------------
+template <bool FAN>
 __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict__ merged, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slope,
                                                      const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                      const float* __restrict__ y2, const float* __restrict__ gain,
-                                                     float* __restrict__ out, int T, int nframes, int Tc, int tw0) {
+                                                     float* __restrict__ out, int T, int nframes, int Tc, int tw0, int nfan) {
     constexpr int YP = C + 4;
     auto gidx = [&](int fr) -> long { return (long)(fr / Tc) * T + tw0 + fr % Tc; };      // time window, see k_qkv_proj_ln
     __shared__ __attribute__((aligned(16))) _Float16 ahi[FR_A];
@@ -488,6 +491,30 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
             v[k].z = rv[k].z + (v[k].z - mean) * rstd * pw[k].z + pb[k].z;
             v[k].w = rv[k].w + (v[k].w - mean) * rstd * pw[k].w + pb[k].w;
         }
+        if (FAN) {
+            // one target after the other, each in the order above (its gain loads, then its stores); `rv` (the residual, used
+            // up by now) takes the gains and then the products: `v` stays the un-gained frame and no third array is live
+            const float* gj = gain + (long)b * nfan * N;
+            long fo = fr + (long)b * (nfan - 1) * T * N;        // frame (b, t) of out row b * nfan
+#pragma unroll 1
+            for (int j = 0; j < nfan; ++j, gj += N, fo += (long)T * N) {
+#pragma unroll
+                for (int k = 0; k < NSLOT; ++k)
+                    rv[k] = *reinterpret_cast<const float4*>(&gj[(long)min(tid + 256 * k, N4 - 1) * 4]);
+#pragma unroll
+                for (int k = 0; k < NSLOT; ++k) pin_here(rv[k]);        // (or a slot's load sinks into its store's branch, behind stores)
+#pragma unroll
+                for (int k = 0; k < NSLOT; ++k) {
+                    rv[k].x = v[k].x * rv[k].x; rv[k].y = v[k].y * rv[k].y; rv[k].z = v[k].z * rv[k].z; rv[k].w = v[k].w * rv[k].w;
+                }
+#pragma unroll
+                for (int k = 0; k < NSLOT; ++k) {
+                    const int i = tid + 256 * k;
+                    if (i < N4) *reinterpret_cast<float4*>(&out[fo + i * 4]) = rv[k];
+                }
+            }
+            continue;
+        }
         if (gain) {
 #pragma unroll
             for (int k = 0; k < NSLOT; ++k)
@@ -584,8 +611,8 @@ extern "C" int lh_proj_ln_res_win(const float* merged, const void* w_pk, const f
         t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL(k_proj_ln_res, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
-                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0);
+    hipLaunchKernelGGL(k_proj_ln_res<false>, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
+                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, 1);
     return check_launch();
 }
 
@@ -593,6 +620,28 @@ extern "C" int lh_proj_ln_res(const float* merged, const void* w_pk, const float
                               const float* ln_w, const float* ln_b, const float* y2, const float* gain, float* out,
                               int B, int T, lh_stream_t stream) {
     return lh_proj_ln_res_win(merged, w_pk, bias, slope, ln_w, ln_b, y2, gain, out, B, T, 0, T, stream);
+}
+
+// fan-out (ABI 25): K gains per utterance, out row b * K + j = the frame of utterance b under gain[b * K + j]
+extern "C" int lh_proj_ln_res_fan_win(const float* merged, const void* w_pk, const float* bias, const float* slope,
+                                      const float* ln_w, const float* ln_b, const float* y2, const float* gain, float* out,
+                                      int B, int T, int t0, int Tc, int K, lh_stream_t stream) {
+    using namespace lh;
+    if (!gain || K < 1) return LH_ERR_ARG;
+    if (K == 1) return lh_proj_ln_res_win(merged, w_pk, bias, slope, ln_w, ln_b, y2, gain, out, B, T, t0, Tc, stream);
+    if (!merged || !w_pk || !bias || !slope || !ln_w || !ln_b || !y2 || !out || B <= 0 || T <= 0 || t0 < 0 || Tc <= 0 ||
+        t0 + Tc > T)
+        return LH_ERR_ARG;
+    const int nframes = B * Tc;
+    hipLaunchKernelGGL(k_proj_ln_res<true>, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
+                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, K);
+    return check_launch();
+}
+
+extern "C" int lh_proj_ln_res_fan(const float* merged, const void* w_pk, const float* bias, const float* slope,
+                                  const float* ln_w, const float* ln_b, const float* y2, const float* gain, float* out,
+                                  int B, int T, int K, lh_stream_t stream) {
+    return lh_proj_ln_res_fan_win(merged, w_pk, bias, slope, ln_w, ln_b, y2, gain, out, B, T, 0, T, K, stream);
 }
 
 #if defined(LH_DBG_K6)

@@ -343,6 +343,33 @@ class Net(_cabi.HipHost, nn.Module):
         x, next_state = self.predict(x, embeds, input_state, pad, want_state=input_state is not None)
         return x
 
+    def forward_many(self, x, embeds, pad=True):
+        """Every enrolled speaker of a mixture in one call: x [B, 2, N], embeds [B, K, 256] -> y [B, K, 2, N], where
+        y[b, k] is `forward(x[b:b+1], embeds[b:b+1, k:k+1])`.  The reference multiplies the embedding in only in front of
+        block 1 (tfgridnet_causal.py:247-251), so the STFT, the input convolution and block 0 run once per MIXTURE (B rows,
+        with the kernels and windows `forward` picks for batch B) and block 0's last kernel stores its frame once per
+        target (`lh_proj_ln_res_fan`); blocks 1 ... and the back end run on the B K rows as `forward` would for that batch.
+        Starts from the zero state and keeps none.  `gemm_mode = "f32all"` (the test-only reference kernels) shares
+        nothing: it runs the K-times-repeated mixtures through `forward`'s path.  A ragged K is the caller's to pad (any
+        embedding, drop the row)."""
+        if embeds.dim() != 3:
+            raise ValueError(f"embeds must be [B, K, {self.spk_emb_dim}], got {tuple(embeds.shape)}")
+        if x.dim() != 3 or embeds.shape[0] != x.shape[0]:
+            raise ValueError(f"x [B, {self.num_ch}, N] and embeds [B, K, {self.spk_emb_dim}] must agree in B, got "
+                             f"{tuple(x.shape)} and {tuple(embeds.shape)}")
+        if embeds.shape[1] < 1:
+            raise ValueError("embeds must hold at least one speaker per mixture (K >= 1)")
+        if self._debug_taps is not None:
+            raise ValueError("forward_many has no stage taps: tap `forward` on one (mixture, speaker) pair")
+        mod = 0
+        if pad:
+            pad_size = (0, self.stft_pad_size) if self.lookahead else (0, 0)
+            x, mod = mod_pad(x, chunk_size=self.stft_chunk_size, pad=pad_size)
+        y = self._separate_many(x, embeds)
+        if mod != 0:
+            y = y[..., :-mod]
+        return y
+
     def make_streamer(self, batch_size: int, device, use_graph: bool = True):
         """Chunked real-time front end (BASELINE configs[1]): see `Streamer`."""
         return Streamer(self, batch_size, device, use_graph)
@@ -550,78 +577,12 @@ class Net(_cabi.HipHost, nn.Module):
             if taps is not None:
                 taps["Z0"], taps["G"] = xa.clone(), ws["gain"].clone()
 
-            rows = Bn * T * F_
             mode = 1 if self.gemm_mode == "f16x3" else 0
-            wkey, bkey = ("_w16", "_b16") if mode else ("_w", "_b")
             K = self._n_time_chunks(Bn, T, mode)
             if K > 1:
                 self._blocks_chunked(lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K)
-            for i in range(self.n_blocks if K == 1 else 0):
-                bp = pk["blocks"][i]
-                bs = state["gridnet_bufs"][f"buf{i}"]
-                h0, c0 = c32(bs["h0"]), c32(bs["c0"])
-                hN, cN = new(h0), new(c0)
-                fuse = mode == 1 and self.fuse_linear
-                # the fused intra path runs the two directions as consecutive launches (the reverse one accumulates into
-                # the forward one's rows): worth it once a single direction fills the GPU, otherwise the unfused kernel
-                # (both directions concurrently) has half the latency (streaming, batch 1)
-                if fuse and Bn * T >= self.fuse_intra_min_frames:
-                    lib.call("lh_intra_block", P(xa), P(bp["intra_w16"]), P(bp["intra_b16"]), P(bp["intra_lin_w2"]),
-                             P(bp["intra_lin_b"]), P(xb), Bn * T, st)
-                elif mode == 1 and Bn * T <= self.stream_intra_max_frames:
-                    # a handful of frames (streaming): one workgroup per (frame, direction), mat-vec recurrence
-                    lib.call("lh_intra_stream", P(xa), P(bp["intra_s_wih"]), P(bp["intra_s_b"]), P(bp["intra_s_whh"]),
-                             P(hbuf), Bn * T, st)
-                    lib.call("lh_linear_res", P(hbuf), P(bp["intra_lin_w"]), P(bp["intra_lin_b"]), P(xa), P(xb), rows,
-                             2 * H_, st)
-                else:
-                    # intra: LN + BiLSTM over frequency -> Linear(128->64) + residual
-                    lib.call("lh_ln_lstm_intra", P(xa), P(bp["intra_ln_w"]), P(bp["intra_ln_b"]), P(bp["intra" + wkey]),
-                             P(bp["intra" + bkey]), P(hbuf), Bn * T, mode, st)
-                    lib.call("lh_linear_res", P(hbuf), P(bp["intra_lin_w"]), P(bp["intra_lin_b"]), P(xa), P(xb), rows,
-                             2 * H_, st)
-                if fuse and Bn * F_ <= self.inter_matvec_max_seqs and T >= 32:
-                    # few sequences, many steps (batch 1 offline): one workgroup per sequence, mat-vec recurrence
-                    lib.call("lh_inter_matvec", P(xb), P(bp["inter_s_wih"]), P(bp["inter_s_b"]), P(bp["inter_s_whh"]),
-                             P(bp["inter_lin_w"]), P(bp["inter_lin_b"]), P(h0), P(c0), P(hN), P(cN), P(xc), Bn, T, st)
-                elif fuse:
-                    lib.call("lh_inter_block", P(xb), P(bp["inter_w8"]), P(bp["inter_b16"]), P(bp["inter_lin_wu"]),
-                             P(bp["inter_lin_b"]), P(h0), P(c0), P(hN), P(cN), P(xc), Bn, T, st)
-                else:
-                    # inter: LN + causal LSTM over time with carried state -> Linear(64->64) + residual
-                    lib.call("lh_ln_lstm_inter", P(xb), P(bp["inter_ln_w"]), P(bp["inter_ln_b"]), P(bp["inter" + wkey]),
-                             P(bp["inter" + bkey]), P(h0), P(c0), P(hN), P(cN), P(hbuf), Bn, T, mode, st)
-                    lib.call("lh_linear_res", P(hbuf), P(bp["inter_lin_w"]), P(bp["inter_lin_b"]), P(xb), P(xc), rows,
-                             H_, st)
-                # attention: history rows in, Q/K/V, local attention (head merge fused), projection + LN + residual
-                if not from_zero:
-                    lib.call("lh_ring_pack", P(c32(bs["K_buf"])), P(c32(bs["V_buf"])), P(ws["kx"]), P(ws["vx"]), Bn, T, st)
-                    ws["hist_dirty"] = True
-                elif ws["hist_dirty"]:                      # history rows of the window-extended buffers back to zero
-                    ws["kx"][:, :hist].zero_()
-                    ws["vx"][:, :hist].zero_()
-                    ws["hist_dirty"] = False
-                lib.call("lh_qkv_proj_ln", P(xc), P(bp["qkv_w"]), P(bp["qkv_b"]), P(bp["qkv_slopes"]), P(bp["lnq_w"]),
-                         P(bp["lnq_b"]), P(bp["lnk_w"]), P(bp["lnk_b"]), P(bp["lnv_w"]), P(bp["lnv_b"]), P(ws["q"]),
-                         P(ws["kx"]), P(ws["vx"]), None, Bn, T, st)
-                lib.call("lh_local_attn", P(ws["q"]), P(ws["kx"]), P(ws["vx"]), P(xb), Bn, T, st)
-                if taps is not None:
-                    taps[f"blocks.{i}.attn"] = xb.clone()          # head-major [B][T][4][97][16]
-                gain = ws["gain"] if (i == 0 and self.n_blocks > 1) else None   # `batch * embed` before block 1
-                lib.call("lh_proj_ln_res", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
-                         P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(gain) if gain is not None else None, P(xa),
-                         Bn, T, st)
-                if want_state:
-                    bs["h0"], bs["c0"] = hN, cN
-                    bs["K_buf"] = torch.empty(Bn * nh, hist, self.E * F_, device=dev, dtype=torch.float32)
-                    bs["V_buf"] = torch.empty(Bn * nh, hist, self.V_dim * F_, device=dev, dtype=torch.float32)
-                    lib.call("lh_ring_unpack", P(ws["kx"]), P(ws["vx"]), P(bs["K_buf"]), P(bs["V_buf"]), Bn, T, st)
-                if taps is not None:
-                    taps[f"blocks.{i}.Y2"] = xc.clone()
-                    taps[f"blocks.{i}.Q"] = unsplit_qk(ws["q"], self.E * F_)
-                    taps[f"blocks.{i}.K"] = unsplit_qk(ws["kx"][:, hist:hist + T], self.E * F_)
-                    taps[f"blocks.{i}.V"] = unsplit_v(ws["vx"][:, hist:hist + T])
-                    taps[f"blocks.{i}.out"] = xa.clone()
+            else:
+                self._blocks_whole(lib, pk, ws, state, Bn, T, dev, from_zero, want_state, mode)
 
             dec_in, ist_in = c32(state["deconv_buf"]), c32(state["istft_buf"])
             dec_out, ist_out = new(dec_in), new(ist_in)
@@ -635,6 +596,150 @@ class Net(_cabi.HipHost, nn.Module):
                 if self.range_status(dev):
                     raise RuntimeError(self._RANGE_MSG.format("this forward"))
         return y, (state if want_state else None)
+
+    def _separate_many(self, x: torch.Tensor, embeds: torch.Tensor) -> torch.Tensor:
+        """`_separate` from the zero state for Kt speakers per mixture (`forward_many`): front end and block 0 on the Bn
+        mixtures, blocks 1 ... and the back end on Bn * Kt rows (row b * Kt + j = mixture b, speaker j), each part with the
+        kernels and windows `_separate` picks for its batch.  `fan` = (gain [Bn * Kt][97][64], out [Bn * Kt][T][97][64], Kt)
+        is what block 0's last stage writes instead of its own batch's `xa`: no stage of block 0 reads that buffer, so its
+        windows may run ahead of each other; the window streams join before block 1 starts."""
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("lookoncetohear_amd.Net is an inference-only drop-in (forward kernels, no autograd): call "
+                               ".eval() and/or run under torch.no_grad(); training stays on the reference model")
+        self._check_gemm_mode()
+        assert x.shape[1] == self.num_ch, "input must be [B, num_ch, N]"
+        Bn, _, n = x.shape
+        Kt = embeds.shape[1]
+        Bk = Bn * Kt
+        embed = embeds.reshape(Bk, -1)
+        if self.gemm_mode == "f32all" or self.n_blocks < 2:       # nothing to share (one block: no gain at all)
+            y, _ = self._separate(x.repeat_interleave(Kt, 0), embed, None, False)
+            return y.view(Bn, Kt, *y.shape[1:])
+        lib = self._lib(x)
+        dev = x.device
+        if self.range_check and int(self._range_flag(dev)[0]) != 0:       # as in `_separate`
+            self._range_flag(dev).zero_()
+            raise RuntimeError(self._RANGE_MSG.format("an earlier forward of this Net"))
+        hop, nfft = self.stft_chunk_size, self.nfft
+        T = (n - nfft) // hop + 1
+        if T < 1:
+            raise ValueError(f"need at least {nfft} samples, got {n}")
+        ns = (T - 1) * hop + nfft
+        x = x[..., :ns].contiguous().float()
+        embed = embed.contiguous().float()
+        with torch.no_grad(), self._device_ctx(x):
+            pk = self._weights(dev)
+            ws, wsk = self._workspace(Bn, T, dev), self._workspace(Bk, T, dev)
+            s0, sk = self._zero_state(Bn, dev), self._zero_state(Bk, dev)
+            st = self._stream(dev)
+            P = lambda t: t.data_ptr()
+            new = lambda t: torch.empty_like(t, dtype=torch.float32)
+            c32 = lambda t: t.contiguous().float()
+            conv_in = c32(s0["conv_buf"]); conv_out = new(conv_in)
+            lib.call("lh_stft_conv_in", P(x), P(conv_in), P(conv_out), P(pk["wfb_t"]), P(pk["conv_w"]),
+                     P(pk["conv_b"]), P(ws["xa"]), Bn, T, ns, st)
+            lib.call("lh_embed_proj_ln", P(embed), P(pk["emb_w"]), P(pk["emb_b"]), P(pk["emb_ln_w"]),
+                     P(pk["emb_ln_b"]), P(wsk["gain_raw"]), P(wsk["gain"]), Bk, st)
+            mode = 1 if self.gemm_mode == "f16x3" else 0
+            fan = (wsk["gain"], wsk["xa"], Kt)
+            for w, s, rows, blocks, f in ((ws, s0, Bn, range(0, 1), fan), (wsk, sk, Bk, range(1, self.n_blocks), None)):
+                K = self._n_time_chunks(rows, T, mode)
+                if K > 1:
+                    self._blocks_chunked(lib, pk, w, s, rows, T, dev, True, False, K, blocks, f)
+                else:
+                    self._blocks_whole(lib, pk, w, s, rows, T, dev, True, False, mode, blocks, f)
+            dec_in, ist_in = c32(sk["deconv_buf"]), c32(sk["istft_buf"])
+            dec_out, ist_out = new(dec_in), new(ist_in)
+            y = torch.empty(Bn, Kt, self.n_srcs, hop * T, device=dev, dtype=torch.float32)
+            lib.call("lh_deconv_istft", P(wsk["xa"]), P(dec_in), P(dec_out), P(ist_in), P(ist_out), P(pk["deconv_w"]),
+                     P(pk["deconv_b"]), P(pk["wfb_dec"]), P(y), P(self._range_flag(dev)), 1, Bk, T, st)
+            if self.range_check == "sync" and not self._capturing():
+                if self.range_status(dev):
+                    raise RuntimeError(self._RANGE_MSG.format("this forward"))
+        return y
+
+    def _blocks_whole(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, mode, blocks=None, fan=None):
+        """The GridNet blocks (tfgridnet_causal.py:489-590) on whole clips: five stage launches per block on the current stream.
+        `blocks`: the block indices to run (all of them by default); `fan`: see `_separate_many`."""
+        F_, nh, H_, hist = self.n_freqs, self.n_head, self.hidden, self.local_atten_len - 1
+        P = lambda t: t.data_ptr()
+        new = lambda t: torch.empty_like(t, dtype=torch.float32)
+        c32 = lambda t: t.contiguous().float()
+        xa, xb, xc, hbuf = ws["xa"], ws["xb"], ws["xc"], ws["hbuf"]
+        st = self._stream(dev)
+        taps = self._debug_taps
+        rows = Bn * T * F_
+        wkey, bkey = ("_w16", "_b16") if mode else ("_w", "_b")
+        for i in (range(self.n_blocks) if blocks is None else blocks):
+            bp = pk["blocks"][i]
+            bs = state["gridnet_bufs"][f"buf{i}"]
+            h0, c0 = c32(bs["h0"]), c32(bs["c0"])
+            hN, cN = new(h0), new(c0)
+            fuse = mode == 1 and self.fuse_linear
+            # the fused intra path runs the two directions as consecutive launches (the reverse one accumulates into
+            # the forward one's rows): worth it once a single direction fills the GPU, otherwise the unfused kernel
+            # (both directions concurrently) has half the latency (streaming, batch 1)
+            if fuse and Bn * T >= self.fuse_intra_min_frames:
+                lib.call("lh_intra_block", P(xa), P(bp["intra_w16"]), P(bp["intra_b16"]), P(bp["intra_lin_w2"]),
+                         P(bp["intra_lin_b"]), P(xb), Bn * T, st)
+            elif mode == 1 and Bn * T <= self.stream_intra_max_frames:
+                # a handful of frames (streaming): one workgroup per (frame, direction), mat-vec recurrence
+                lib.call("lh_intra_stream", P(xa), P(bp["intra_s_wih"]), P(bp["intra_s_b"]), P(bp["intra_s_whh"]),
+                         P(hbuf), Bn * T, st)
+                lib.call("lh_linear_res", P(hbuf), P(bp["intra_lin_w"]), P(bp["intra_lin_b"]), P(xa), P(xb), rows,
+                         2 * H_, st)
+            else:
+                # intra: LN + BiLSTM over frequency -> Linear(128->64) + residual
+                lib.call("lh_ln_lstm_intra", P(xa), P(bp["intra_ln_w"]), P(bp["intra_ln_b"]), P(bp["intra" + wkey]),
+                         P(bp["intra" + bkey]), P(hbuf), Bn * T, mode, st)
+                lib.call("lh_linear_res", P(hbuf), P(bp["intra_lin_w"]), P(bp["intra_lin_b"]), P(xa), P(xb), rows,
+                         2 * H_, st)
+            if fuse and Bn * F_ <= self.inter_matvec_max_seqs and T >= 32:
+                # few sequences, many steps (batch 1 offline): one workgroup per sequence, mat-vec recurrence
+                lib.call("lh_inter_matvec", P(xb), P(bp["inter_s_wih"]), P(bp["inter_s_b"]), P(bp["inter_s_whh"]),
+                         P(bp["inter_lin_w"]), P(bp["inter_lin_b"]), P(h0), P(c0), P(hN), P(cN), P(xc), Bn, T, st)
+            elif fuse:
+                lib.call("lh_inter_block", P(xb), P(bp["inter_w8"]), P(bp["inter_b16"]), P(bp["inter_lin_wu"]),
+                         P(bp["inter_lin_b"]), P(h0), P(c0), P(hN), P(cN), P(xc), Bn, T, st)
+            else:
+                # inter: LN + causal LSTM over time with carried state -> Linear(64->64) + residual
+                lib.call("lh_ln_lstm_inter", P(xb), P(bp["inter_ln_w"]), P(bp["inter_ln_b"]), P(bp["inter" + wkey]),
+                         P(bp["inter" + bkey]), P(h0), P(c0), P(hN), P(cN), P(hbuf), Bn, T, mode, st)
+                lib.call("lh_linear_res", P(hbuf), P(bp["inter_lin_w"]), P(bp["inter_lin_b"]), P(xb), P(xc), rows,
+                         H_, st)
+            # attention: history rows in, Q/K/V, local attention (head merge fused), projection + LN + residual
+            if not from_zero:
+                lib.call("lh_ring_pack", P(c32(bs["K_buf"])), P(c32(bs["V_buf"])), P(ws["kx"]), P(ws["vx"]), Bn, T, st)
+                ws["hist_dirty"] = True
+            elif ws["hist_dirty"]:                      # history rows of the window-extended buffers back to zero
+                ws["kx"][:, :hist].zero_()
+                ws["vx"][:, :hist].zero_()
+                ws["hist_dirty"] = False
+            lib.call("lh_qkv_proj_ln", P(xc), P(bp["qkv_w"]), P(bp["qkv_b"]), P(bp["qkv_slopes"]), P(bp["lnq_w"]),
+                     P(bp["lnq_b"]), P(bp["lnk_w"]), P(bp["lnk_b"]), P(bp["lnv_w"]), P(bp["lnv_b"]), P(ws["q"]),
+                     P(ws["kx"]), P(ws["vx"]), None, Bn, T, st)
+            lib.call("lh_local_attn", P(ws["q"]), P(ws["kx"]), P(ws["vx"]), P(xb), Bn, T, st)
+            if taps is not None:
+                taps[f"blocks.{i}.attn"] = xb.clone()          # head-major [B][T][4][97][16]
+            gain = ws["gain"] if (i == 0 and self.n_blocks > 1) else None   # `batch * embed` before block 1
+            if fan is not None and i == 0:
+                lib.call("lh_proj_ln_res_fan", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
+                         P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(fan[0]), P(fan[1]), Bn, T, fan[2], st)
+            else:
+                lib.call("lh_proj_ln_res", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
+                         P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(gain) if gain is not None else None, P(xa),
+                         Bn, T, st)
+            if want_state:
+                bs["h0"], bs["c0"] = hN, cN
+                bs["K_buf"] = torch.empty(Bn * nh, hist, self.E * F_, device=dev, dtype=torch.float32)
+                bs["V_buf"] = torch.empty(Bn * nh, hist, self.V_dim * F_, device=dev, dtype=torch.float32)
+                lib.call("lh_ring_unpack", P(ws["kx"]), P(ws["vx"]), P(bs["K_buf"]), P(bs["V_buf"]), Bn, T, st)
+            if taps is not None:
+                taps[f"blocks.{i}.Y2"] = xc.clone()
+                taps[f"blocks.{i}.Q"] = unsplit_qk(ws["q"], self.E * F_)
+                taps[f"blocks.{i}.K"] = unsplit_qk(ws["kx"][:, hist:hist + T], self.E * F_)
+                taps[f"blocks.{i}.V"] = unsplit_v(ws["vx"][:, hist:hist + T])
+                taps[f"blocks.{i}.out"] = xa.clone()
 
     def _n_time_chunks(self, Bn: int, T: int, mode: int) -> int:
         """Windows the block loop is cut into (see `time_chunks` / `time_chunks_small` in __init__); 1 for streaming-size
@@ -691,10 +796,12 @@ class Net(_cabi.HipHost, nn.Module):
             raise ValueError("chunk_min_frames must cover the attention history (49 frames) on concurrent streams")
         return _Lanes(dev, pool[:K - 1])
 
-    def _blocks_chunked(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K):
+    def _blocks_chunked(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K, blocks=None, fan=None):
         """The three GridNet blocks (tfgridnet_causal.py:489-590) with the time axis cut into K windows, window k on stream k:
         for block i and window k the five stage launches of `_separate` through the `_win` entry points, with two cross-stream
-        dependences per (block, window) — the inter LSTM's (h, c) and the K / V rows of the previous window."""
+        dependences per (block, window) — the inter LSTM's (h, c) and the K / V rows of the previous window.
+        `blocks`: the block indices to run (all of them by default); `fan`: see `_separate_many`."""
+        blocks = range(self.n_blocks) if blocks is None else blocks
         F_, nh, hist = self.n_freqs, self.n_head, self.local_atten_len - 1
         P = lambda t: t.data_ptr()
         c32 = lambda t: t.contiguous().float()
@@ -710,12 +817,12 @@ class Net(_cabi.HipHost, nn.Module):
             ws["hist_dirty_b"] = [False] * self.n_blocks
         bounds = self._window_bounds(Bn, T, K)
         # per block: (h, c) of every window boundary; history rows in place (on the current stream, before the fork)
-        hs, cs = [], []
-        for i in range(self.n_blocks):
+        hs, cs = {}, {}
+        for i in blocks:
             bs = state["gridnet_bufs"][f"buf{i}"]
             h0, c0 = c32(bs["h0"]).reshape(-1, self.hidden), c32(bs["c0"]).reshape(-1, self.hidden)
-            hs.append([h0] + [torch.empty_like(h0) for _ in range(K)])
-            cs.append([c0] + [torch.empty_like(c0) for _ in range(K)])
+            hs[i] = [h0] + [torch.empty_like(h0) for _ in range(K)]
+            cs[i] = [c0] + [torch.empty_like(c0) for _ in range(K)]
             kx, vx = ws["kxb"][i], ws["vxb"][i]
             if not from_zero:
                 lib.call("lh_ring_pack", P(c32(bs["K_buf"])), P(c32(bs["V_buf"])), P(kx), P(vx), Bn, T, self._stream(dev))
@@ -729,7 +836,7 @@ class Net(_cabi.HipHost, nn.Module):
                 if i == 0:
                     ws["hist_dirty"] = False
         lanes.fork()
-        for i in range(self.n_blocks):
+        for i in blocks:
             bp = pk["blocks"][i]
             kx, vx = ws["kxb"][i], ws["vxb"][i]
             gain = ws["gain"] if (i == 0 and self.n_blocks > 1) else None
@@ -768,12 +875,16 @@ class Net(_cabi.HipHost, nn.Module):
                     if k > 0:
                         lanes.wait(k, ev_prev)
                     lib.call("lh_local_attn_win", P(ws["q"]), P(kx), P(vx), P(xb), Bn, T, t0, Tc, st)
-                    lib.call("lh_proj_ln_res_win", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
-                             P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(gain) if gain is not None else None, P(xa),
-                             Bn, T, t0, Tc, st)
+                    if fan is not None and i == 0:
+                        lib.call("lh_proj_ln_res_fan_win", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
+                                 P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(fan[0]), P(fan[1]), Bn, T, t0, Tc, fan[2], st)
+                    else:
+                        lib.call("lh_proj_ln_res_win", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
+                                 P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(gain) if gain is not None else None, P(xa),
+                                 Bn, T, t0, Tc, st)
         lanes.join()
         if want_state:
-            for i in range(self.n_blocks):
+            for i in blocks:
                 bs = state["gridnet_bufs"][f"buf{i}"]
                 bs["h0"], bs["c0"] = hs[i][K].reshape(1, -1, self.hidden), cs[i][K].reshape(1, -1, self.hidden)
                 bs["K_buf"] = torch.empty(Bn * nh, hist, self.E * F_, device=dev, dtype=torch.float32)
