@@ -73,7 +73,7 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (24); bumped on any signature change. */
+/* ABI version of this header (26); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -288,6 +288,28 @@ int lh_proj_ln_res_fan_win(const float* merged, const void* w_pk, const float* b
 int lh_deconv_istft(const float* y, const float* deconv_buf_in, float* deconv_buf_out, const float* istft_buf_in,
                     float* istft_buf_out, const void* wdec_pk, const float* bdec, const void* wfb_dec,
                     float* wave_out, unsigned* range_flag, int keep_nonfinite, int B, int T, lh_stream_t stream);
+
+/* Tap products (ABI 26): the last block's A.3.6 and A.4 as one pair, from the ZERO state and with no state out (an offline
+ * forward).  The transposed conv's channel contraction P[t][f][(kt,kf,o)] = sum_c Y[t][f][c] Wd[c][o][kt][kf] is linear and per
+ * (frame, bin), so the stage that makes Y does it while Y is in registers:
+ *   lh_proj_ln_res_taps   lh_proj_ln_res without gain that stores, instead of the frame, its 36 tap products
+ *                         p_out [B][T][97][36] (0.5625 of the frame's bytes) and the frame maximum fmax [B][T] = max |Y[b][t]|
+ *                         (bounds the spectra in lh_taps_istft).  wdec_pk = lh_deconv_istft's tap image, the rest as above;
+ *                         `_win`: frames [t0, t0 + Tc) like lh_proj_ln_res_win.
+ *   lh_taps_istft         lh_deconv_istft from there: 9-term gather, spectrum re-pack, synthesis, overlap-add.  The carried
+ *                         conv halo and spectrum are zero.  wdec_pk is only read for the bound W1.  wave_out, range_flag and
+ *                         keep_nonfinite as in lh_deconv_istft; lh_set_tuning key 6 applies.
+ * Same groups of rows under one power of two, same accumulator chains, same sum order: wave_out has the BITS of
+ * lh_proj_ln_res(gain = NULL) -> lh_deconv_istft on zero deconv_buf_in / istft_buf_in.
+ * LH_ERR_ARG: a null pointer (range_flag may be NULL), B <= 0, T <= 0, a window outside [0, T). */
+int lh_proj_ln_res_taps(const float* merged, const void* w_pk, const float* bias, const float* slope, const float* ln_w,
+                        const float* ln_b, const float* y2, const void* wdec_pk, float* p_out, float* fmax, int B, int T,
+                        lh_stream_t stream);
+int lh_proj_ln_res_taps_win(const float* merged, const void* w_pk, const float* bias, const float* slope, const float* ln_w,
+                            const float* ln_b, const float* y2, const void* wdec_pk, float* p_out, float* fmax, int B, int T,
+                            int t0, int Tc, lh_stream_t stream);
+int lh_taps_istft(const float* p, const float* fmax, const void* wdec_pk, const float* bdec, const void* wfb_dec,
+                  float* wave_out, unsigned* range_flag, int keep_nonfinite, int B, int T, lh_stream_t stream);
 
 /* ---- time windows (ABI 14) ------------------------------------------------------------------------------------------------
  * Every stage of a GridNetBlock is causal in time (tfgridnet_causal.py:489-590): the intra pass is per frame, the inter LSTM

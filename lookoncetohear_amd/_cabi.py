@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -82,6 +82,11 @@ SIGNATURES = {
     # several enrolled speakers per mixture (ABI 25): block 0's last stage stored once per target, Net.forward_many
     "lh_proj_ln_res_fan": [_P] * 9 + [_I, _I, _I, _P],
     "lh_proj_ln_res_fan_win": [_P] * 9 + [_I, _I, _I, _I, _I, _P],
+    # tap products (ABI 26): the last block's closing stage emits the deconv tap products, the back end starts from them
+    # (zero state in, no state out: Net.fuse_taps)
+    "lh_proj_ln_res_taps": [_P] * 10 + [_I, _I, _P],
+    "lh_proj_ln_res_taps_win": [_P] * 10 + [_I, _I, _I, _I, _P],
+    "lh_taps_istft": [_P] * 7 + [_I, _I, _I, _P],
     "lh_emb_frontend": [_P] * 10 + [_I, _I, _I, _P],
     "lh_emb_axis_fused": [_P] * 8 + [_I, _I, _I, _I, _I, _P],
     "lh_emb_axis_mv": [_P] * 9 + [_I, _I, _I, _I, _P],

@@ -454,6 +454,224 @@ __global__ void __launch_bounds__(BE_NT) k_deconv_istft(const float* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The back end on TAP PRODUCTS (lh_taps_istft, ABI 26).  From the zero state with no state wanted, the last block's
+// closing stage (k_proj_ln_res<.., TAPS>, lh_pointwise.hip) has already contracted the channels: it wrote
+// P [B][T][97][36] and the frame maxima M [B][T] that k_deconv_istft makes for itself in its staging and product phases
+// (83 % of its frame loop).  What is left is k_deconv_istft without those two phases: the same persistent grid, tiles and
+// runs, the same ring slots (fr + 4) & 3 for P and M, written at the same points of the loop, the same gather order, spectrum
+// split, synthesis and overlap-add — so the waveform has the bits of lh_proj_ln_res -> lh_deconv_istft on zero state buffers.
+// Halo frames -2, -1 and the carried spectrum are zero (their products and maxima too), no state is written.
+// ------------------------------------------------------------------------------------------------------
+constexpr int TI_PQ = NF * BE_NP / 4;                       // float4 per frame of P (873)
+constexpr int TI_NLD = (TI_PQ + BE_NT - 1) / BE_NT;         // per thread and frame (2)
+constexpr int TI_RING = 4;                                  // frames in flight per workgroup (8 float4 per thread)
+
+__global__ void __launch_bounds__(BE_NT) k_taps_istft(const float* __restrict__ p, const float* __restrict__ fmax,
+                                                      const _Float16* __restrict__ wd_pk, const float* __restrict__ bd,
+                                                      const _Float16* __restrict__ wfb_pk, float* __restrict__ wave_out,
+                                                      unsigned* __restrict__ range_flag, int keep_nonfinite, int B, int T,
+                                                      int runs_per_b) {
+    // partial products of 4 frames; bin f sits in row f + 1, rows 0 and 98 stay zero (the f -/+ 1 taps of the edge bins)
+    __shared__ __attribute__((aligned(16))) float pring[4][NF + 2][BE_PP];
+    __shared__ __attribute__((aligned(16))) _Float16 sxh[NSRC * BE_SA];             // A image of the 16 spectra
+    __shared__ __attribute__((aligned(16))) _Float16 sxl[NSRC * BE_SA];
+    __shared__ __attribute__((aligned(16))) float frs[BE_NJ][NSRC][BE_FP];         // synthesis frames
+    __shared__ float fmaxr[4];                        // M[fr] ring, slot (fr + 4) & 3 like the partial products
+    __shared__ __attribute__((aligned(16))) float sinv[BE_NJ];
+    __shared__ float w1s[48];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(tid), g4 = lane >> 4, l15 = lane & 15;
+
+    const bool synth = wave < 6;
+    float bias4[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) bias4[o] = bd[o];
+    const float bmax = fmaxf(fmaxf(fabsf(bias4[0]), fabsf(bias4[1])), fmaxf(fabsf(bias4[2]), fabsf(bias4[3])));
+    if (tid < 4) fmaxr[tid] = 0.f;
+    if (tid < BE_NJ) sinv[tid] = 0.f;
+    if (tid < 48) {                               // L1 norm of tap column tid (|hi| + |lo| >= |w|), fragment order: the W1 bound
+        float a = 0.f;
+        for (int k = 0; k < C; ++k) {
+            const int idx = (((tid >> 4) * 2 + (k >> 5)) * 64 + ((k >> 3) & 3) * 16 + (tid & 15)) * 16 + (k & 7);
+            a += fabsf((float)wd_pk[idx]) + fabsf((float)wd_pk[idx + 8]);
+        }
+        w1s[tid] = a;
+    }
+    static_assert((NSRC * BE_SA) % 8 == 0, "16-byte zero fill");
+    const f16x8 z8 = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = tid; i < NSRC * BE_SA / 8; i += BE_NT) {     // k-padding of the spectra: multiplies zero weights, must be finite
+        *reinterpret_cast<f16x8*>(&sxh[i * 8]) = z8;
+        *reinterpret_cast<f16x8*>(&sxl[i * 8]) = z8;
+    }
+    // guard rows 0 and 98 and the pad columns 36..39 are never written again
+    for (int i = tid; i < 4 * (NF + 2) * BE_PP; i += BE_NT) (&pring[0][0][0])[i] = 0.f;
+    __syncthreads();
+    float W1 = 0.f;
+    for (int i = 0; i < 48; ++i) W1 = fmaxf(W1, w1s[i]);
+    W1 *= 3.0f;                                   // three frequency taps per frame
+
+    const int tiles_per_b = (T + BE_TT - 1) / BE_TT;
+    const int n_runs = B * runs_per_b;
+    const long L = (long)HOP * T;
+    // runs of consecutive tiles of one utterance, as in k_deconv_istft
+    int run = blockIdx.x, tk = 0, k1 = 0;
+    for (;;) {
+        bool first = false;
+        if (tk == k1) {
+            if (run >= n_runs) break;
+            const int rb0 = run % runs_per_b;
+            tk = (int)((long)tiles_per_b * rb0 / runs_per_b);
+            k1 = (int)((long)tiles_per_b * (rb0 + 1) / runs_per_b);
+            first = true;
+        }
+        const int b = run / runs_per_b;
+        {
+        const int t0 = tk * BE_TT;
+        const int nt_out = min(BE_TT, T - t0);
+        const bool cont = !first;                     // ring and Sx[15] of the previous tile are this tile's history
+        const int tv = tid + (tk >> 30);              // always tid: keeps the per-thread addresses inside the tile loop (k_deconv_istft)
+        __syncthreads();
+
+        // one spectrum value -> row jd of source s's A image
+        auto put_sx = [&](int jd, int s, int k, float v) {
+            _Float16 h, l;
+            split_hl(v, h, l);
+            const int idx = s * BE_SA + a_index<BE_NJ>(jd, k);
+            sxh[idx] = h;
+            sxl[idx] = l;
+        };
+        // Sx frame 0: the zero spectrum in front of the clip, the previous tile's last frame (inside a run), or recomputed
+        // from the halo frames (first tile of a later run)
+        if (t0 == 0) {                                // (workgroup-uniform)
+            static_assert(NSRC * NK <= BE_NT, "one carried spectrum value per thread");
+            float sc, iv;
+            pow2_scale<12>(0.f, sc, iv);
+            if (tid < NSRC * NK) put_sx(0, tid / NK, tid % NK, 0.f * sc);
+            if (tid == 0) sinv[0] = iv;
+        } else if (cont) {
+            for (int i = tid; i < NSRC * NK; i += BE_NT) {
+                const int s = i / NK, k = i % NK;
+                const int src = s * BE_SA + a_index<BE_NJ>(BE_TT, k), dst = s * BE_SA + a_index<BE_NJ>(0, k);
+                sxh[dst] = sxh[src];
+                sxl[dst] = sxl[src];
+            }
+            if (tid == 0) sinv[0] = sinv[BE_TT];
+        }                                             // (the frame loop's first barrier is behind these before row 15 is rewritten)
+
+        // input frames t0-3 .. t0+nt_out-1 ; after frame fr has arrived, output frame td = fr is complete
+        struct PFrame { f32x4 a, b; float m; };       // a frame of P in flight: float4 tv and tv + 512 of its 873, and M (vector
+                                                      // values, not float4 structs: a struct only ever copied stays a stack object)
+        static_assert(TI_NLD == 2 && TI_RING == 4, "two float4 per thread and frame, two pairs of frames in flight");
+        PFrame r0, r1, r2, r3;
+        const unsigned eoff0 = (unsigned)tv * 16u, eoff1 = (unsigned)min(tv + BE_NT, TI_PQ - 1) * 16u;
+        const char* pb = reinterpret_cast<const char*>(p) + (long)b * T * (TI_PQ * 16);
+        const float* fb = fmax + (long)b * T;
+        auto load_frame_p = [&](int fr, PFrame& d) __attribute__((always_inline)) {       // 0 <= fr < T
+            const char* base = pb + (long)fr * (TI_PQ * 16);
+            d.a = *reinterpret_cast<const f32x4*>(base + eoff0);
+            d.b = *reinterpret_cast<const f32x4*>(base + eoff1);
+            d.m = fb[fr];
+        };
+        static_assert(BE_NP == 36, "9 float4 per row of P");
+        auto put_frame = [&](int slot, const PFrame& s) __attribute__((always_inline)) {  // rows of 36 floats -> rows 1..97 of the slot
+            *reinterpret_cast<f32x4*>(&pring[slot][tv / 9 + 1][(tv % 9) * 4]) = s.a;
+            const int j = tv + BE_NT;
+            if (j < TI_PQ) *reinterpret_cast<f32x4*>(&pring[slot][j / 9 + 1][(j % 9) * 4]) = s.b;
+        };
+        const int fr_first = cont ? t0 : max(t0 - 3, -2);   // frames below -2 do not exist (their taps see nothing)
+        const int fr_end = t0 + nt_out;
+        // frames fr, fr + 1 (the second may not exist) arrive in the ring, output frames td = fr, fr + 1 are complete
+        auto pair = [&](int fr, PFrame& x, PFrame& y) __attribute__((always_inline)) {
+            const bool two = fr + 1 < fr_end;
+            __syncthreads();                          // the previous pair's gather has read the slots rewritten now
+            if (fr < 0) {                             // frames -2, -1: the zero state — products and maxima zero
+                for (int i = tv; i < 2 * NF * BE_PP; i += BE_NT) pring[2 + i / (NF * BE_PP)][1 + (i / BE_PP) % NF][i % BE_PP] = 0.f;
+                if (tid < 2) fmaxr[2 + tid] = 0.f;
+            } else {
+                put_frame((fr + 4) & 3, x);
+                if (two) put_frame((fr + 5) & 3, y);
+                if (tid == 0) {
+                    fmaxr[(fr + 4) & 3] = x.m;
+                    if (two) fmaxr[(fr + 5) & 3] = y.m;
+                }
+            }
+            // Refill UNCONDITIONALLY, the index clamped to the tile: past its end the tile's last frame is loaded again and
+            // never used (k_deconv_istft on why).  fr + TI_RING >= 2: never a frame of the zero state
+            load_frame_p(min(fr + TI_RING, fr_end - 1), x);
+            load_frame_p(min(fr + 1 + TI_RING, fr_end - 1), y);
+            __syncthreads();
+
+            // output frames td = fr, fr + 1: D[o][f] = b[o] + sum_{kt,kf} P[td-kt][f+1-kf][(kt*3+kf)*4 + o]
+            for (int i = tv; i < (two ? 2 : 1) * NF; i += BE_NT) {      // one (frame, bin) per thread: its 4 outputs together
+                const int q = i >= NF, f = i - NF * q;
+                const int td = fr + q;
+                if (td < t0 - 1 || td < 0) continue;
+                const int jd = td + 1 - t0;           // Sx frame index inside the tile
+                float4 v = make_float4(bias4[0], bias4[1], bias4[2], bias4[3]);
+#pragma unroll
+                for (int kt = 0; kt < 3; ++kt) {
+                    const int ps = (td - kt + 4) & 3;         // td >= 0, so frame td - kt >= -2 exists (zero state)
+#pragma unroll
+                    for (int kf = 0; kf < 3; ++kf) {          // guard rows: no bounds
+                        const float4 pv = *reinterpret_cast<const float4*>(&pring[ps][f + 2 - kf][(kt * 3 + kf) * 4]);
+                        v.x += pv.x; v.y += pv.y; v.z += pv.z; v.w += pv.w;
+                    }
+                }
+                const float vo[4] = {v.x, v.y, v.z, v.w};
+                float ssx, isx;
+                pow2_scale<14>(fmaf(W1, fmaxr[(td + 4) & 3] + fmaxr[(td + 3) & 3] + fmaxr[(td + 2) & 3], bmax), ssx, isx);
+                if (f == 0) sinv[jd] = isx;
+#pragma unroll
+                for (int o = 0; o < 4; ++o) put_sx(jd, o >> 1, (o & 1) * NF + f, vo[o] * ssx);
+            }
+        };
+        // TI_RING frames in flight (frames -2, -1, the first pair of a clip's first tile, are not loaded)
+        if (fr_first >= 0) { load_frame_p(min(fr_first, fr_end - 1), r0); load_frame_p(min(fr_first + 1, fr_end - 1), r1); }
+        load_frame_p(min(fr_first + 2, fr_end - 1), r2);      // fr_first + 2 >= 0
+        load_frame_p(min(fr_first + 3, fr_end - 1), r3);
+        for (int fbase = fr_first; fbase < fr_end; fbase += TI_RING) {
+            pair(fbase, r0, r1);
+            if (fbase + 2 < fr_end) pair(fbase + 2, r2, r3);
+        }
+        __syncthreads();
+
+        // synthesis: fr[jd][s][n] = sum_k Sx[jd][s][k] Wdec[k][n]; row tile = the 16 frames of a source, waves 0..5
+        // own 2 of the 12 column tiles of 16 samples each
+        if (synth) {
+#pragma unroll 1
+            for (int i = 0; i < 2; ++i) {             // one column tile at a time: 56 registers of B fragments
+                f16x8 wfh[BE_SK], wfl[BE_SK];
+                load_w<BE_SK>(wfb_pk, 2 * wave + i, lane, wfh, wfl);
+#pragma unroll
+                for (int s = 0; s < NSRC; ++s) {
+                    const f32x4 acc = mma_tile<BE_NJ, BE_SK>(sxh + s * BE_SA, sxl + s * BE_SA, 0, g4, l15, wfh, wfl, 0.f);
+                    const float4 iv4 = *reinterpret_cast<const float4*>(&sinv[g4 * 4]);      // 1 / scale of spectra g4*4 ..
+                    const float iv[4] = {iv4.x, iv4.y, iv4.z, iv4.w};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) frs[g4 * 4 + r][s][(2 * wave + i) * 16 + l15] = acc[r] * iv[r];
+                }
+            }
+        }
+        __syncthreads();
+
+        // overlap-add: output frame t (samples 128t..128t+127) = fr[t+1][0:128] + fr[t][128:192]
+        bool bad = false;
+        for (int i = tid; i < nt_out * NSRC * HOP; i += BE_NT) {
+            const int n = i % HOP, s = (i / HOP) % NSRC, jt = i / (HOP * NSRC);
+            float v = frs[jt + 1][s][n];
+            if (n < NFFT - HOP) v += frs[jt][s][n + HOP];
+            // inf / NaN: the caller's flag word is raised and the sample stored as the caller asked (k_deconv_istft)
+            const bool nf = (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+            wave_out[((long)b * NSRC + s) * L + (long)(t0 + jt) * HOP + n] = (nf && !keep_nonfinite) ? 0.f : v;
+            bad |= nf;
+        }
+        if (bad && range_flag) __hip_atomic_store(range_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        // (the next tile's first barrier orders these frs reads before its synthesis, several barriers later, rewrites them)
+        }
+        if (++tk == k1) run += gridDim.x;
+    }
+}
+
 static int g_runs_per_b = 0;            // lh_set_tuning key 6: runs per utterance (0 = automatic); tests force 1 on tiny batches
 int backend_set_runs(int v) {
     if (v < 0) return LH_ERR_ARG;
@@ -486,6 +704,21 @@ extern "C" int lh_deconv_istft(const float* y, const float* deconv_buf_in, float
     hipLaunchKernelGGL(k_deconv_istft, dim3(n_runs < 256 ? n_runs : 256), dim3(BE_NT), 0, (hipStream_t)stream, y,
                        deconv_buf_in, deconv_buf_out, istft_buf_in, istft_buf_out, (const _Float16*)wdec_pk, bdec,
                        (const _Float16*)wfb_dec, wave_out, range_flag, keep_nonfinite, B, T, runs_per_b);
+    return check_launch();
+}
+
+extern "C" int lh_taps_istft(const float* p, const float* fmax, const void* wdec_pk, const float* bdec, const void* wfb_dec,
+                             float* wave_out, unsigned* range_flag, int keep_nonfinite, int B, int T, lh_stream_t stream) {
+    using namespace lh;
+    if (!p || !fmax || !wdec_pk || !bdec || !wfb_dec || !wave_out || B <= 0 || T <= 0) return LH_ERR_ARG;
+    // the run split of lh_deconv_istft (same lh_set_tuning key 6)
+    const int tiles_per_b = (T + BE_TT - 1) / BE_TT;
+    int runs_per_b = g_runs_per_b ? g_runs_per_b : 256 / B;
+    runs_per_b = runs_per_b < 1 ? 1 : (runs_per_b > tiles_per_b ? tiles_per_b : runs_per_b);
+    const int n_runs = B * runs_per_b;
+    hipLaunchKernelGGL(k_taps_istft, dim3(n_runs < 256 ? n_runs : 256), dim3(BE_NT), 0, (hipStream_t)stream, p, fmax,
+                       (const _Float16*)wdec_pk, bdec, (const _Float16*)wfb_dec, wave_out, range_flag, keep_nonfinite, B, T,
+                       runs_per_b);
     return check_launch();
 }
 

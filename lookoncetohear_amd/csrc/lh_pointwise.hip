@@ -2,6 +2,7 @@
 //   k_linear_res   out = res + W h + b                            (intra_linear / inter_linear + residual)
 //   k_qkv_proj_ln  Q/K/V = LN_(f,e)(PReLU(W y + b)) per head       (attn_conv_Q/K/V)
 //   k_proj_ln_res  out = (y2 + LN_(f,c)(PReLU(W m + b))) * gain    (attn_concat_proj + residual + speaker gain)
+//                  TAPS (last block): P = out . Wd, the 36 deconv tap products per (frame, bin), instead of `out`
 //
 // These are HBM-streaming stages: every activation byte should cross HBM once per stage, so
 //   * workgroups are persistent (grid-stride over row tiles / frames) and keep their weights in VGPRs;
@@ -379,20 +380,38 @@ __device__ float lh_dbg_part[8 * 24 * 256 * 4];
 // attn_concat_proj + LN over (f,c) + residual (+ speaker gain); persistent, grid-stride over frames
 // FAN (lh_proj_ln_res_fan, ABI 25): `nfan` speaker gains per utterance — gain [B * nfan][97][64], out [B * nfan][T][97][64]; the
 // un-gained frame is computed once and stored nfan times, row b * nfan + j under gain[b * nfan + j]
+// TAPS (lh_proj_ln_res_taps, ABI 26): the last block's frame only feeds the transposed conv of the back end, whose channel
+// contraction P[f][(kt,kf,o)] = sum_c Y[f][c] Wd[c][o][kt][kf] is linear and per (frame, bin).  It runs here, on the finished
+// values in `v`, with the arithmetic of k_deconv_istft (lh_backend.hip) bit for bit: the same eight row groups share a
+// power of two, the same hi / lo split, the same two accumulator chains.  The frame is not stored: `out` receives
+// P [frames][97][36] (0.5625 of the frame's bytes) and `fmax` the frame maximum max |Y| that bounds the spectra there.
 // ------------------------------------------------------------------------------------------------------
-template <bool FAN>
+constexpr int TAP_NP = 36;                  // tap columns (kt, kf, o); the B image pads them to 48
+constexpr int TAP_W = 3 * 2 * 64 * 16;      // halves of the packed taps: 3 column tiles x 2 k-steps x 64 lanes x [hi 8 | lo 8]
+template <bool FAN, bool TAPS = false>
 __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict__ merged, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slope,
                                                      const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                      const float* __restrict__ y2, const float* __restrict__ gain,
-                                                     float* __restrict__ out, int T, int nframes, int Tc, int tw0, int nfan) {
+                                                     float* __restrict__ out, int T, int nframes, int Tc, int tw0, int nfan,
+                                                     const _Float16* __restrict__ wd_pk, float* __restrict__ fmax) {
+    static_assert(!(FAN && TAPS), "the tap products are the last block's output: no gain, no fan-out");
     constexpr int YP = C + 4;
     auto gidx = [&](int fr) -> long { return (long)(fr / Tc) * T + tw0 + fr % Tc; };      // time window, see k_qkv_proj_ln
     __shared__ __attribute__((aligned(16))) _Float16 ahi[FR_A];
     __shared__ __attribute__((aligned(16))) _Float16 alo[FR_A];
     __shared__ __attribute__((aligned(16))) float ys[NF * YP];
     __shared__ float red[4];
+    // TAPS: the packed taps as B fragments, 1 / scale of every row of the split frame, the waves' frame maxima
+    __shared__ __attribute__((aligned(16))) _Float16 wds[TAPS ? TAP_W : 8];
+    __shared__ __attribute__((aligned(16))) float rinv[TAPS ? FR_RP : 4];
+    __shared__ float wm[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(tid), g4 = lane >> 4, l15 = lane & 15;
+    if (TAPS) {
+        for (int i = tid; i < TAP_W / 8; i += 256)
+            *reinterpret_cast<f16x8*>(&wds[i * 8]) = *reinterpret_cast<const f16x8*>(&wd_pk[i * 8]);
+        if (tid < FR_RP - NF) rinv[NF + tid] = 0.f;            // pad rows: finite
+    }                                       // (the first frame's staging barrier orders these before their readers)
 
     f16x8 wh[2], wl[2];
     load_w<2>(w_pk, wave, lane, wh, wl);   // wave w owns output channels 16w .. 16w+15
@@ -515,6 +534,80 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
             }
             continue;
         }
+        if (TAPS) {
+            // The frame -> the (free) A images, split like k_deconv_istft::stage_frame: rows r with (r & 31) >> 2 == g share one
+            // power of two.  Slot k holds row (tid >> 4) + 16 k, so group `wave` is this wave's even slots and group
+            // `wave + 4` its odd ones.  The back end staged 4 float4 per thread on 512 threads with the element index
+            // clamped to the frame, so every group but 0 also saw the frame's LAST float4 (row 96, channels 60..63) — here
+            // slot 6 of every thread but the first 16, clamped the same way: it joins both maxima.
+            const int tx = tid + (fidx >> 30);      // always tid: keeps this phase's per-thread addresses out of the frame loop's registers
+            float me = 0.f, mo = 0.f;
+#pragma unroll
+            for (int k = 0; k < NSLOT; k += 2) me = fmaxf(me, absmax4(v[k]));
+#pragma unroll
+            for (int k = 1; k < NSLOT; k += 2) mo = fmaxf(mo, absmax4(v[k]));
+            static_assert(NSLOT == 7 && N4 - 1 - 256 * (NSLOT - 1) == 15, "slot 6: row 96 in threads 0..15, the clamped last float4 elsewhere");
+            if (tid >= 16) mo = fmaxf(mo, absmax4(v[NSLOT - 1]));
+            const float ge = wave_max_uniform(me), go = wave_max_uniform(mo);
+            float sce, ive, sco, ivo;
+            pow2_scale<FR_TE>(ge, sce, ive);
+            pow2_scale<FR_TE>(go, sco, ivo);
+#pragma unroll
+            for (int k = 0; k < NSLOT; ++k) {
+                const int i = tx + 256 * k;
+                const float sc = (k & 1) ? sco : sce;
+                if (i < N4) {
+                    store_split4<FR_RP>(ahi, alo, i >> 4, (i & 15) * 4, make_float4(v[k].x * sc, v[k].y * sc, v[k].z * sc, v[k].w * sc));
+                    if ((i & 15) == 0) rinv[i >> 4] = (k & 1) ? ivo : ive;
+                }
+            }
+            if (lane == 0) wm[wave] = fmaxf(ge, go);
+            __syncthreads();                  // image, rinv and wm complete (the statistics' barriers are behind every read of ys)
+            // P = Y (97 x 64) . Wd (64 x 48): wave w owns row tiles w and w + 4, three column tiles each; per tile the chains of
+            // the back end — am: hi.hi, ac: hi.lo then lo.hi, k-steps ascending — and (am + ac) * rinv[row]
+#pragma unroll 1
+            for (int mt = wave; mt < FR_RP / 16; mt += 4) {
+                const int ln = lane + (mt >> 30);     // always lane: keeps the tap fragments' reads inside the loop (48 registers)
+                f16x8 ah[2], al[2];
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const int idx = a_slot<FR_RP>(ks * 4 + g4, mt * 16 + l15);
+                    ah[ks] = *reinterpret_cast<const f16x8*>(&ahi[idx]);
+                    al[ks] = *reinterpret_cast<const f16x8*>(&alo[idx]);
+                }
+                const float4 iv4 = *reinterpret_cast<const float4*>(&rinv[mt * 16 + g4 * 4]);
+                const float iv[4] = {iv4.x, iv4.y, iv4.z, iv4.w};
+#pragma unroll
+                for (int nt = 0; nt < 3; ++nt) {
+                    f32x4 am = f32x4{0.f, 0.f, 0.f, 0.f}, ac = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {
+                        const f16x8 th = *reinterpret_cast<const f16x8*>(&wds[((nt * 2 + ks) * 64 + ln) * 16]);
+                        const f16x8 tl = *reinterpret_cast<const f16x8*>(&wds[((nt * 2 + ks) * 64 + ln) * 16 + 8]);
+                        am = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], th, am, 0, 0, 0);
+                        ac = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ks], tl, ac, 0, 0, 0);
+                        ac = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[ks], th, ac, 0, 0, 0);
+                    }
+                    const int col = nt * 16 + l15;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int f = mt * 16 + g4 * 4 + r;
+                        if (f < NF && col < TAP_NP) ys[f * TAP_NP + col] = (am[r] + ac[r]) * iv[r];
+                    }
+                }
+            }
+            __syncthreads();                  // P complete in ys; the A reads are behind the next frame's frame_store
+            const long gf = gidx(fidx);
+            float* pd = out + gf * (NF * TAP_NP);
+            constexpr int PQ = NF * TAP_NP / 4;       // 873 float4, rows of 36 floats back to back
+#pragma unroll
+            for (int k = 0; k < (PQ + 255) / 256; ++k) {
+                const int i = tx + 256 * k;
+                if (i < PQ) *reinterpret_cast<float4*>(&pd[i * 4]) = *reinterpret_cast<const float4*>(&ys[i * 4]);
+            }
+            if (tid == 0) fmax[gf] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+            continue;                         // (the next frame's staging barrier orders these ys reads before ys is rewritten)
+        }
         if (gain) {
 #pragma unroll
             for (int k = 0; k < NSLOT; ++k)
@@ -611,8 +704,9 @@ extern "C" int lh_proj_ln_res_win(const float* merged, const void* w_pk, const f
         t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL(k_proj_ln_res<false>, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
-                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, 1);
+    hipLaunchKernelGGL((k_proj_ln_res<false, false>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
+                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, 1, (const _Float16*)nullptr,
+                       (float*)nullptr);
     return check_launch();
 }
 
@@ -620,6 +714,27 @@ extern "C" int lh_proj_ln_res(const float* merged, const void* w_pk, const float
                               const float* ln_w, const float* ln_b, const float* y2, const float* gain, float* out,
                               int B, int T, lh_stream_t stream) {
     return lh_proj_ln_res_win(merged, w_pk, bias, slope, ln_w, ln_b, y2, gain, out, B, T, 0, T, stream);
+}
+
+// tap products (ABI 26): the last block's stage in front of lh_taps_istft — p_out [B][T][97][36], fmax [B][T]
+extern "C" int lh_proj_ln_res_taps_win(const float* merged, const void* w_pk, const float* bias, const float* slope,
+                                       const float* ln_w, const float* ln_b, const float* y2, const void* wdec_pk, float* p_out,
+                                       float* fmax, int B, int T, int t0, int Tc, lh_stream_t stream) {
+    using namespace lh;
+    if (!merged || !w_pk || !bias || !slope || !ln_w || !ln_b || !y2 || !wdec_pk || !p_out || !fmax || B <= 0 || T <= 0 ||
+        t0 < 0 || Tc <= 0 || t0 + Tc > T)
+        return LH_ERR_ARG;
+    const int nframes = B * Tc;
+    hipLaunchKernelGGL((k_proj_ln_res<false, true>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                       merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, (const float*)nullptr, p_out, T, nframes, Tc,
+                       t0, 1, (const _Float16*)wdec_pk, fmax);
+    return check_launch();
+}
+
+extern "C" int lh_proj_ln_res_taps(const float* merged, const void* w_pk, const float* bias, const float* slope,
+                                   const float* ln_w, const float* ln_b, const float* y2, const void* wdec_pk, float* p_out,
+                                   float* fmax, int B, int T, lh_stream_t stream) {
+    return lh_proj_ln_res_taps_win(merged, w_pk, bias, slope, ln_w, ln_b, y2, wdec_pk, p_out, fmax, B, T, 0, T, stream);
 }
 
 // fan-out (ABI 25): K gains per utterance, out row b * K + j = the frame of utterance b under gain[b * K + j]
@@ -633,8 +748,9 @@ extern "C" int lh_proj_ln_res_fan_win(const float* merged, const void* w_pk, con
         t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL(k_proj_ln_res<true>, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
-                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, K);
+    hipLaunchKernelGGL((k_proj_ln_res<true, false>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
+                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, K, (const _Float16*)nullptr,
+                       (float*)nullptr);
     return check_launch();
 }
 

@@ -257,6 +257,11 @@ class Net(_cabi.HipHost, nn.Module):
         self._range_flags: Dict[str, torch.Tensor] = {}
         # fused LSTM + Linear + residual kernels (f16x3 mode only); LOOKONCE_FUSE=0 selects the unfused pair
         self.fuse_linear = os.environ.get("LOOKONCE_FUSE", "1") != "0"
+        # An offline forward (zero state in, no state out) lets the LAST block's closing stage emit the 36 deconv tap products
+        # per (frame, bin) instead of the 64-channel frame, and the back end start from them (lh_proj_ln_res_taps ->
+        # lh_taps_istft: the same waveform bits, 0.875 frame passes over HBM less; profiles/taps_fusion_ab.txt).
+        # LOOKONCE_FUSE_TAPS=0 keeps lh_proj_ln_res -> lh_deconv_istft.
+        self.fuse_taps = os.environ.get("LOOKONCE_FUSE_TAPS", "1") != "0"
         # fused intra kernel (two launches, one per direction) from here on, the unfused pair (both directions concurrently) below:
         # 8192 frames in rounds 1-5; with time windows the crossover is lower (profiles/r06h: B = 13 x 625 frames 3.40 -> 3.08 ms,
         # B = 10 2.66 -> 2.60, B = 8 2.32 -> 2.36)
@@ -579,23 +584,46 @@ class Net(_cabi.HipHost, nn.Module):
 
             mode = 1 if self.gemm_mode == "f16x3" else 0
             K = self._n_time_chunks(Bn, T, mode)
+            # tap products instead of the last block's frame: zero state in, nothing out, no stage taps (the last block has no
+            # gain: only block 0 applies one, and with a single block nobody does)
+            ptaps = None
+            if self.fuse_taps and from_zero and taps is None:
+                ptaps = self._tap_buffers(ws, Bn, T, dev, own=K > 1)
             if K > 1:
-                self._blocks_chunked(lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K)
+                self._blocks_chunked(lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K, ptaps=ptaps)
             else:
-                self._blocks_whole(lib, pk, ws, state, Bn, T, dev, from_zero, want_state, mode)
+                self._blocks_whole(lib, pk, ws, state, Bn, T, dev, from_zero, want_state, mode, ptaps=ptaps)
 
-            dec_in, ist_in = c32(state["deconv_buf"]), c32(state["istft_buf"])
-            dec_out, ist_out = new(dec_in), new(ist_in)
             y = torch.empty(Bn, self.n_srcs, hop * T, device=dev, dtype=torch.float32)
             flag = self._range_flag(dev)
-            lib.call("lh_deconv_istft", P(xa), P(dec_in), P(dec_out), P(ist_in), P(ist_out), P(pk["deconv_w"]),
-                     P(pk["deconv_b"]), P(pk["wfb_dec"]), P(y), P(flag), 1, Bn, T, st)
+            if ptaps is not None:
+                lib.call("lh_taps_istft", P(ptaps[0]), P(ptaps[1]), P(pk["deconv_w"]), P(pk["deconv_b"]), P(pk["wfb_dec"]),
+                         P(y), P(flag), 1, Bn, T, st)
+            else:
+                dec_in, ist_in = c32(state["deconv_buf"]), c32(state["istft_buf"])
+                dec_out, ist_out = new(dec_in), new(ist_in)
+                lib.call("lh_deconv_istft", P(xa), P(dec_in), P(dec_out), P(ist_in), P(ist_out), P(pk["deconv_w"]),
+                         P(pk["deconv_b"]), P(pk["wfb_dec"]), P(y), P(flag), 1, Bn, T, st)
             if want_state:
                 state["conv_buf"], state["deconv_buf"], state["istft_buf"] = conv_out, dec_out, ist_out
             if self.range_check == "sync" and not self._capturing():
                 if self.range_status(dev):
                     raise RuntimeError(self._RANGE_MSG.format("this forward"))
         return y, (state if want_state else None)
+
+    def _tap_buffers(self, ws, Bn, T, dev, own):
+        """(P [B][T][97][36], fmax [B][T]) of `lh_proj_ln_res_taps` / `lh_taps_istft`.  On whole clips P lives in the storage of
+        `xa`: the last block's closing stage is the only writer of `xa` and nothing reads it afterwards.  With time windows
+        (`own`) a later window's intra stage still reads ITS frames of `xa` while an earlier window writes P — frame t of P is
+        not where frame t of `xa` is — so P gets storage of its own, allocated on first use."""
+        n = Bn * T * self.n_freqs * 36
+        if "fmax" not in ws:
+            ws["fmax"] = torch.empty(Bn * T, device=dev, dtype=torch.float32)
+        if not own:
+            return ws["xa"].view(-1)[:n], ws["fmax"]
+        if "ptaps" not in ws:
+            ws["ptaps"] = torch.empty(n, device=dev, dtype=torch.float32)
+        return ws["ptaps"], ws["fmax"]
 
     def _separate_many(self, x: torch.Tensor, embeds: torch.Tensor) -> torch.Tensor:
         """`_separate` from the zero state for Kt speakers per mixture (`forward_many`): front end and block 0 on the Bn
@@ -658,9 +686,10 @@ class Net(_cabi.HipHost, nn.Module):
                     raise RuntimeError(self._RANGE_MSG.format("this forward"))
         return y
 
-    def _blocks_whole(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, mode, blocks=None, fan=None):
+    def _blocks_whole(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, mode, blocks=None, fan=None, ptaps=None):
         """The GridNet blocks (tfgridnet_causal.py:489-590) on whole clips: five stage launches per block on the current stream.
-        `blocks`: the block indices to run (all of them by default); `fan`: see `_separate_many`."""
+        `blocks`: the block indices to run (all of them by default); `fan`: see `_separate_many`; `ptaps`: (P, fmax) the last
+        block's closing stage writes instead of its frame (`_separate`, `fuse_taps`)."""
         F_, nh, H_, hist = self.n_freqs, self.n_head, self.hidden, self.local_atten_len - 1
         P = lambda t: t.data_ptr()
         new = lambda t: torch.empty_like(t, dtype=torch.float32)
@@ -725,6 +754,9 @@ class Net(_cabi.HipHost, nn.Module):
             if fan is not None and i == 0:
                 lib.call("lh_proj_ln_res_fan", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
                          P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(fan[0]), P(fan[1]), Bn, T, fan[2], st)
+            elif ptaps is not None and i == self.n_blocks - 1 and gain is None:
+                lib.call("lh_proj_ln_res_taps", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
+                         P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(pk["deconv_w"]), P(ptaps[0]), P(ptaps[1]), Bn, T, st)
             else:
                 lib.call("lh_proj_ln_res", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
                          P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(gain) if gain is not None else None, P(xa),
@@ -796,11 +828,11 @@ class Net(_cabi.HipHost, nn.Module):
             raise ValueError("chunk_min_frames must cover the attention history (49 frames) on concurrent streams")
         return _Lanes(dev, pool[:K - 1])
 
-    def _blocks_chunked(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K, blocks=None, fan=None):
+    def _blocks_chunked(self, lib, pk, ws, state, Bn, T, dev, from_zero, want_state, K, blocks=None, fan=None, ptaps=None):
         """The three GridNet blocks (tfgridnet_causal.py:489-590) with the time axis cut into K windows, window k on stream k:
         for block i and window k the five stage launches of `_separate` through the `_win` entry points, with two cross-stream
         dependences per (block, window) — the inter LSTM's (h, c) and the K / V rows of the previous window.
-        `blocks`: the block indices to run (all of them by default); `fan`: see `_separate_many`."""
+        `blocks`: the block indices to run (all of them by default); `fan`: see `_separate_many`; `ptaps`: see `_blocks_whole`."""
         blocks = range(self.n_blocks) if blocks is None else blocks
         F_, nh, hist = self.n_freqs, self.n_head, self.local_atten_len - 1
         P = lambda t: t.data_ptr()
@@ -878,6 +910,10 @@ class Net(_cabi.HipHost, nn.Module):
                     if fan is not None and i == 0:
                         lib.call("lh_proj_ln_res_fan_win", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
                                  P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(fan[0]), P(fan[1]), Bn, T, t0, Tc, fan[2], st)
+                    elif ptaps is not None and i == self.n_blocks - 1 and gain is None:
+                        lib.call("lh_proj_ln_res_taps_win", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
+                                 P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(pk["deconv_w"]), P(ptaps[0]), P(ptaps[1]), Bn, T,
+                                 t0, Tc, st)
                     else:
                         lib.call("lh_proj_ln_res_win", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
                                  P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(gain) if gain is not None else None, P(xa),
