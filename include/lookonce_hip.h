@@ -87,7 +87,11 @@ int lh_abi_version(void);
  * every wave raised during the on-chain / off-chain phase of the step), key 9 = issue priority in k_inter_xp (0 = none,
  * 1 / 2 = the LayerNorm / projection waves, 3 = every wave during the on-chain phase: default, 4 = off-chain phase; + 16 = the
  * two roles on the other four waves: A/B only, 6-8 % slower),
- * key 16 = issue priority for the on-chain MFMAs of the embedder's recurrent kernel k_emb_rec (0 = off: default, 1 = on). */
+ * key 16 = issue priority for the on-chain MFMAs of the embedder's recurrent kernel k_emb_rec (0 = off: default, 1 = on),
+ * key 19 = cache policy of the frame kernels' once-touched streams (csrc/lh_cachepol.h): 0 = plain accesses always, 1 = non-temporal
+ * when the launch's frame stream is at least 256 MiB (default), 2 = at any size — in the launches that have a policy at all:
+ * lh_qkv_proj_ln_rows and the one-tile attention shape (clips of at most 16 frames, or key 4 = 1) are streaming paths and run
+ * plain accesses under every value; outputs do not depend on the key; other values: LH_ERR_ARG. */
 int lh_set_tuning(int key, int value);
 
 /* Validates model_params (reference net.py:21-49 / configs/tsh.json:5-19) against the compiled constants. */

@@ -20,6 +20,7 @@
 // the shared 49 rows from that XCD's L2 instead of HBM.  kx / vx carry KV_PAD zero rows behind row T+48: tiles
 // read (never need) up to 47 rows past their last key and 0 * finite = 0.
 #include "lh_common.h"
+#include "lh_cachepol.h"
 
 namespace lh {
 
@@ -39,7 +40,7 @@ __device__ unsigned long long lh_attn_trace_buf[16];
 #else
 #define AT_STAMP(k) do { } while (0)
 #endif
-template <int MQ, int RING, int TQ = 16 * MQ>
+template <int MQ, int RING, int TQ = 16 * MQ, int POL = 0>      // POL: cache policy of Q, K, V and merged (lh_cachepol.h)
 __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restrict__ q, const _Float16* __restrict__ kx,
                                                        const _Float16* __restrict__ vx, float* __restrict__ merged,
                                                        int BH, int T, int ntt, int tw0, int tend) {
@@ -85,14 +86,14 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
 #pragma unroll
             for (int mq = 0; mq < MQ; ++mq) {
                 const _Float16* p = qb + qoff[mq] + s * 64;
-                dq[mq].h = *reinterpret_cast<const f16x8*>(p);
-                dq[mq].l = *reinterpret_cast<const f16x8*>(p + 8);
+                dq[mq].h = cp::ld_h8<POL, cp::ATT_Q_LD>(p);
+                dq[mq].l = cp::ld_h8<POL, cp::ATT_Q_LD>(p + 8);
             }
 #pragma unroll
             for (int nt = 0; nt < NKT; ++nt) {
                 const _Float16* p = kb + koff[nt] + s * 64;
-                dk[nt].h = *reinterpret_cast<const f16x8*>(p);
-                dk[nt].l = *reinterpret_cast<const f16x8*>(p + 8);
+                dk[nt].h = cp::ld_h8<POL, cp::ATT_K_LD>(p);
+                dk[nt].l = cp::ld_h8<POL, cp::ATT_K_LD>(p + 8);
             }
         };
         auto mma = [&](const Frag (&sq)[MQ], const Frag (&sk)[NKT]) {
@@ -200,8 +201,14 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                 }
                 const _Float16* p = vb + r * LDVH + qc;
                 VQuad v;
-                v.h = *reinterpret_cast<const f16x4*>(p);
-                v.l = *reinterpret_cast<const f16x4*>(p + 4);
+                if constexpr (cp::nt(POL, cp::ATT_V_LD)) {        // one 16-byte access, as the plain pair of 8-byte ones is merged into
+                    const f16x8 hl = cp::ld_h8<POL, cp::ATT_V_LD>(p);
+                    v.h = f16x4{hl[0], hl[1], hl[2], hl[3]};
+                    v.l = f16x4{hl[4], hl[5], hl[6], hl[7]};
+                } else {
+                    v.h = *reinterpret_cast<const f16x4*>(p);
+                    v.l = *reinterpret_cast<const f16x4*>(p + 4);
+                }
                 ring[slot][j] = v;
             }
         };
@@ -256,8 +263,8 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                     for (int r = 0; r < 4; ++r) {
                         const int t = t0 + mq * 16 + g4 * 4 + r;
                         if (t < tend && (TQ == 16 * MQ || mq * 16 + g4 * 4 + r < TQ))      // head-major slab [b][t][hd][f][v]: one head's frame is 6208 contiguous bytes
-                            *reinterpret_cast<float4*>(&merged[(((long)b * T + t) * NH + hd) * DV + col]) =
-                                make_float4(am[mq][0][r], am[mq][1][r], am[mq][2][r], am[mq][3][r]);
+                            cp::st_f4<POL, cp::ATT_MERGED_ST>(&merged[(((long)b * T + t) * NH + hd) * DV + col],
+                                                              make_float4(am[mq][0][r], am[mq][1][r], am[mq][2][r], am[mq][3][r]));
                     }
             }
         }
@@ -383,12 +390,19 @@ extern "C" int lh_local_attn_win(const void* q, const void* kx, const void* vx, 
     // latency-bound launches (a handful of workgroups): split the V columns of a tile over 7 workgroups
     const dim3 grid(bh8 * ntt, bh8 * ntt <= 64 ? 7 : 1);
     const _Float16 *qh = (const _Float16*)q, *kh = (const _Float16*)kx, *vh = (const _Float16*)vx;
+    // cache policy by the footprint of the launch's largest stream (merged; V is as large): lh_cachepol.h.  The one-tile
+    // shape is the streaming chunk's and stays plain.
+    const bool pol = cp::nt_on((long)B * Tc * NF * C * 4);
     if (mq == 1)
-        hipLaunchKernelGGL((k_local_attn<1, 3>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<1, 3, 16, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+    else if (mq == 3 && pol)
+        hipLaunchKernelGGL((k_local_attn<3, 2, 40, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
     else if (mq == 3)
-        hipLaunchKernelGGL((k_local_attn<3, 2, 40>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<3, 2, 40, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+    else if (pol)
+        hipLaunchKernelGGL((k_local_attn<2, 2, 32, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
     else
-        hipLaunchKernelGGL((k_local_attn<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<2, 2, 32, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
     return check_launch();
 }
 

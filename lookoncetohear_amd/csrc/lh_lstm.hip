@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "lh_common.h"
+#include "lh_cachepol.h"
 
 namespace lh {
 
@@ -1050,6 +1051,10 @@ int launch_inter_xp(const float* x, const void* w_pk, const float* b_sum, const 
 }
 namespace lh { int backend_set_runs(int v); } // lh_backend.hip
 namespace lh { int snap_set_tiles(int v); }   // lh_stream.hip
+namespace lh { namespace cp {                 // lh_cachepol.h: one cache-policy switch for every kernel source
+static int g_nt_mode = 1;                     // lh_set_tuning(19, v): 0 = never non-temporal, 1 = by the launch's footprint, 2 = always
+int nt_mode() { return g_nt_mode; }
+} }
 #if defined(LH_PROBE_TRACE)
 extern "C" int lh_probe_trace_read(unsigned long long* host_dst) {
     return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(lh::lh_trace_buf), sizeof(lh::lh_trace_buf)) == hipSuccess ? 0 : 1;
@@ -1061,6 +1066,11 @@ extern "C" int lh_set_tuning(int key, int value) {
     if (key >= 7 && key < 16) return lh::xp_set(key, value);      // lh_recur.hip switches
     if (key == 16 || key == 17) return lh::emb_set(key, value);   // lh_embed.hip: k_emb_rec issue priority, attention GEMM variant
     if (key == 18) return lh::snap_set_tiles(value);              // lh_stream.hip: tiles per item of the *_rows snapshot kernels
+    if (key == 19) {                                              // cache policy of the activation streams (lh_cachepol.h)
+        if (value < 0 || value > 2) return LH_ERR_ARG;
+        lh::cp::g_nt_mode = value;
+        return LH_OK;
+    }
     if (key < 0 || key >= 8) return LH_ERR_ARG;
 #if defined(LH_LEGACY)
     if (key == 3) lh::g_dephase = value;

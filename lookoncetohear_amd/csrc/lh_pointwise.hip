@@ -146,7 +146,7 @@ struct HeadLN {
         return v;
     }
     // normalise + affine + split -> the row in global memory
-    template <int VLAYOUT>
+    template <int VLAYOUT, int POL = 0>
     __device__ __forceinline__ void store(float rstd, _Float16* dst, int lane) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
@@ -158,12 +158,11 @@ struct HeadLN {
             if (live(lane, k)) {
                 const int qd = lane + 64 * k;
                 if (VLAYOUT) {
-                    *reinterpret_cast<f16x8*>(&dst[8 * qd]) =
-                        f16x8{h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]};
+                    cp::st_h8<POL, cp::QKV_ST>(&dst[8 * qd], f16x8{h01[0], h01[1], h23[0], h23[1], l01[0], l01[1], l23[0], l23[1]});
                 } else {
                     _Float16* d = dst + 8 * qd - 4 * (qd & 1);
-                    *reinterpret_cast<f16x4*>(d) = f16x4{h01[0], h01[1], h23[0], h23[1]};
-                    *reinterpret_cast<f16x4*>(d + 8) = f16x4{l01[0], l01[1], l23[0], l23[1]};
+                    cp::st_h4<POL, cp::QKV_ST>(d, f16x4{h01[0], h01[1], h23[0], h23[1]});
+                    cp::st_h4<POL, cp::QKV_ST>(d + 8, f16x4{l01[0], l01[1], l23[0], l23[1]});
                 }
             }
         }
@@ -246,7 +245,8 @@ __device__ __forceinline__ void qkv_products(const _Float16* ahi, const _Float16
 // in the persistent loop: the lock-step instantiation sits at 249 of 256 VGPRs and stays, instruction for instruction, the
 // code it was.  With ROWS (T = Tc = 1, tw0 = 0) `ring_pos` is write_pos[B]: frame b writes its K / V rows into ring slot
 // write_pos[b], a negative entry writes neither (a held or idle row: its Q row is still written, from the zero-gated input).
-template <bool ROWS>
+// POL (lh_cachepol.h): 0 = plain accesses, 1 = the frame load and the Q / K / V stores as the stream table says
+template <bool ROWS, int POL = 0>
 __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict__ y, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slopes,
                                                      const float* __restrict__ lnq_w, const float* __restrict__ lnq_b,
@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
     aq.load_affine(lnq_w, lnq_b, lane);
     ak.load_affine(lnk_w, lnk_b, lane);
     float4 stg[FR_NLD];
-    if ((int)blockIdx.x < nframes) frame_load(y + gidx(blockIdx.x) * NF * C, tid, stg);
+    if ((int)blockIdx.x < nframes) frame_load<POL, cp::QKV_X_LD>(y + gidx(blockIdx.x) * NF * C, tid, stg);
     const long tkp = T + HIST + KV_PAD;
     // K / V row of frame t: HIST + t behind the history rows — or, for a one-frame chunk on a persistent ring
     // (ring_pos != NULL, T = 1), slot (*ring_pos mod 50): the 50 rows are then exactly the attention window, in
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
         frame_store_scaled(ahi, alo, rinv, tid, stg);
         __syncthreads();                      // image complete; also orders the previous frame's reads of `yf`
         QKV_STAMP(1);
-        if (fr + (int)gridDim.x < nframes) frame_load(y + gidx(fr + gridDim.x) * NF * C, tid, stg);   // prefetch
+        if (fr + (int)gridDim.x < nframes) frame_load<POL, cp::QKV_X_LD>(y + gidx(fr + gridDim.x) * NF * C, tid, stg);   // prefetch
 
         // The 7 row tiles as a software pipeline (stage m: LDS reads of tile m + 1 | MFMAs of tile m | epilogue of tile m - 1),
         // unrolled so that every LDS address is an immediate: qkv_products above.  PReLU as max / min when all three slopes
@@ -348,8 +348,8 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
             const float mq = wave_sum(sq1) * (1.0f / DQK), mk = wave_sum(sk1) * (1.0f / DQK);
             const float vq = lq.center(mq, ln), vk = lk.center(mk, ln);
             const float rq = rsqrtf(wave_sum(vq) * (1.0f / DQK) + LN_EPS), rk = rsqrtf(wave_sum(vk) * (1.0f / DQK) + LN_EPS);
-            lq.store<0>(rq, qrow, ln);
-            if (!ROWS || wp >= 0) lk.store<0>(rk, krow_p, ln);
+            lq.template store<0, POL>(rq, qrow, ln);
+            if (!ROWS || wp >= 0) lk.template store<0, POL>(rk, krow_p, ln);
         }
         QKV_STAMP(4);
         if (!ROWS || wp >= 0) {
@@ -359,7 +359,7 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
             const float mv = wave_sum(sv1) * (1.0f / DV);
             const float vv = lv.center(mv, ln);
             const float rv = rsqrtf(wave_sum(vv) * (1.0f / DV) + LN_EPS);
-            lv.store<1>(rv, vrow, ln);
+            lv.template store<1, POL>(rv, vrow, ln);
         }
         QKV_STAMP(5);
     }
@@ -388,7 +388,7 @@ __device__ float lh_dbg_part[8 * 24 * 256 * 4];
 // ------------------------------------------------------------------------------------------------------
 constexpr int TAP_NP = 36;                  // tap columns (kt, kf, o); the B image pads them to 48
 constexpr int TAP_W = 3 * 2 * 64 * 16;      // halves of the packed taps: 3 column tiles x 2 k-steps x 64 lanes x [hi 8 | lo 8]
-template <bool FAN, bool TAPS = false>
+template <bool FAN, bool TAPS = false, int POL = 0>      // POL: cache policy of merged, the residual and the output (lh_cachepol.h)
 __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict__ merged, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slope,
                                                      const float* __restrict__ lnw, const float* __restrict__ lnb,
@@ -430,19 +430,19 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
 
     frame_zero_pad(ahi, alo, tid);
     float4 stg[FR_NLD];
-    if ((int)blockIdx.x < nframes) frame_load_heads(merged + gidx(blockIdx.x) * N, tid, stg);
+    if ((int)blockIdx.x < nframes) frame_load_heads<POL, cp::PROJ_MERGED_LD>(merged + gidx(blockIdx.x) * N, tid, stg);
     for (int fidx = blockIdx.x; fidx < nframes; fidx += gridDim.x) {     // grid-stride over frames (b*T + t)
         const int b = fidx / Tc;
         const long fr = gidx(fidx) * N;
         frame_store(ahi, alo, tid, stg);
         __syncthreads();                      // image complete; also orders the previous frame's reads of `ys`
-        if (fidx + (int)gridDim.x < nframes) frame_load_heads(merged + gidx(fidx + gridDim.x) * N, tid, stg);
+        if (fidx + (int)gridDim.x < nframes) frame_load_heads<POL, cp::PROJ_MERGED_LD>(merged + gidx(fidx + gridDim.x) * N, tid, stg);
 
         // residual rows of this frame: loads in flight during the MFMA + statistics phases
         float4 rv[NSLOT];
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k)
-            rv[k] = *reinterpret_cast<const float4*>(&y2[fr + (long)min(tid + 256 * k, N4 - 1) * 4]);
+            rv[k] = cp::ld_f4<POL, cp::PROJ_RES_LD>(&y2[fr + (long)min(tid + 256 * k, N4 - 1) * 4]);
 
         // row tiles 0..5 hold rows 0..95 (all valid); only tile 6 (rows 96..111, one valid) needs the bounds check
         // (round 5: one accumulator chain, PReLU as max / min when the slope allows it — see k_qkv_proj_ln)
@@ -529,7 +529,7 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
 #pragma unroll
                 for (int k = 0; k < NSLOT; ++k) {
                     const int i = tid + 256 * k;
-                    if (i < N4) *reinterpret_cast<float4*>(&out[fo + i * 4]) = rv[k];
+                    if (i < N4) cp::st_f4<POL, cp::PROJ_ST>(&out[fo + i * 4], rv[k]);
                 }
             }
             continue;
@@ -603,7 +603,7 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
 #pragma unroll
             for (int k = 0; k < (PQ + 255) / 256; ++k) {
                 const int i = tx + 256 * k;
-                if (i < PQ) *reinterpret_cast<float4*>(&pd[i * 4]) = *reinterpret_cast<const float4*>(&ys[i * 4]);
+                if (i < PQ) cp::st_f4<POL, cp::PROJ_ST>(&pd[i * 4], *reinterpret_cast<const float4*>(&ys[i * 4]));
             }
             if (tid == 0) fmax[gf] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
             continue;                         // (the next frame's staging barrier orders these ys reads before ys is rewritten)
@@ -620,7 +620,7 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) {
             const int i = tid + 256 * k;
-            if (i < N4) *reinterpret_cast<float4*>(&out[fr + i * 4]) = v[k];
+            if (i < N4) cp::st_f4<POL, cp::PROJ_ST>(&out[fr + i * 4], v[k]);
         }
     }
 }
@@ -668,9 +668,15 @@ extern "C" int lh_qkv_proj_ln_win(const float* y, const void* w_pk, const float*
         !vx || B <= 0 || T <= 0 || (ring_pos && T != 1) || t0 < 0 || Tc <= 0 || t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL(k_qkv_proj_ln<false>, dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
-                       (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
-                       (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
+    // cache policy by the footprint of the launch's largest stream (the frames of x; V is as large): lh_cachepol.h
+    if (cp::nt_on((long)nframes * NF * C * 4))
+        hipLaunchKernelGGL((k_qkv_proj_ln<false, 1>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
+                           (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
+                           (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
+    else
+        hipLaunchKernelGGL((k_qkv_proj_ln<false, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
+                           (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
+                           (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
     return check_launch();
 }
 
@@ -690,7 +696,7 @@ extern "C" int lh_qkv_proj_ln_rows(const float* y, const void* w_pk, const float
     if (!y || !w_pk || !bias || !slopes || !lnq_w || !lnq_b || !lnk_w || !lnk_b || !lnv_w || !lnv_b || !q || !kx || !vx ||
         !write_pos || B <= 0)
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_qkv_proj_ln<true>, dim3(B < 512 ? B : 512), dim3(256), 0, (hipStream_t)stream, y,
+    hipLaunchKernelGGL((k_qkv_proj_ln<true, 0>), dim3(B < 512 ? B : 512), dim3(256), 0, (hipStream_t)stream, y,
                        (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
                        (_Float16*)kx, (_Float16*)vx, 1, B, write_pos, 1, 0);
     return check_launch();
@@ -704,9 +710,14 @@ extern "C" int lh_proj_ln_res_win(const float* merged, const void* w_pk, const f
         t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL((k_proj_ln_res<false, false>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
-                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, 1, (const _Float16*)nullptr,
-                       (float*)nullptr);
+    if (cp::nt_on((long)nframes * NF * C * 4))
+        hipLaunchKernelGGL((k_proj_ln_res<false, false, 1>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, 1,
+                           (const _Float16*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((k_proj_ln_res<false, false, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, 1,
+                           (const _Float16*)nullptr, (float*)nullptr);
     return check_launch();
 }
 
@@ -725,9 +736,14 @@ extern "C" int lh_proj_ln_res_taps_win(const float* merged, const void* w_pk, co
         t0 < 0 || Tc <= 0 || t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL((k_proj_ln_res<false, true>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
-                       merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, (const float*)nullptr, p_out, T, nframes, Tc,
-                       t0, 1, (const _Float16*)wdec_pk, fmax);
+    if (cp::nt_on((long)nframes * NF * C * 4))
+        hipLaunchKernelGGL((k_proj_ln_res<false, true, 1>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, (const float*)nullptr, p_out, T, nframes, Tc,
+                           t0, 1, (const _Float16*)wdec_pk, fmax);
+    else
+        hipLaunchKernelGGL((k_proj_ln_res<false, true, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, (const float*)nullptr, p_out, T, nframes, Tc,
+                           t0, 1, (const _Float16*)wdec_pk, fmax);
     return check_launch();
 }
 
@@ -748,9 +764,14 @@ extern "C" int lh_proj_ln_res_fan_win(const float* merged, const void* w_pk, con
         t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
-    hipLaunchKernelGGL((k_proj_ln_res<true, false>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, merged,
-                       (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, K, (const _Float16*)nullptr,
-                       (float*)nullptr);
+    if (cp::nt_on((long)nframes * NF * C * 4))
+        hipLaunchKernelGGL((k_proj_ln_res<true, false, 1>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, K,
+                           (const _Float16*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((k_proj_ln_res<true, false, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           merged, (const _Float16*)w_pk, bias, slope, ln_w, ln_b, y2, gain, out, T, nframes, Tc, t0, K,
+                           (const _Float16*)nullptr, (float*)nullptr);
     return check_launch();
 }
 

@@ -5,6 +5,7 @@
 // an absolute 2^-25 below that, the three partial products go into ONE fp32 accumulator, and a split costs no multiply.
 #pragma once
 #include "lh_common.h"
+#include "lh_cachepol.h"
 
 namespace lh {
 
@@ -107,19 +108,22 @@ constexpr int FR_RP = 112;
 constexpr int FR_A = 2 * 4 * FR_RP * 8;    // halves per image (K = 64 -> 2 k-steps)
 constexpr int FR_NLD = (NF * 16 + 255) / 256;
 
+// POL / S: cache policy of the stream the frame belongs to (lh_cachepol.h); the default is the plain load
+template <int POL = 0, unsigned S = 0>
 __device__ __forceinline__ void frame_load(const float* __restrict__ src, int tid, float4 (&stg)[FR_NLD]) {
 #pragma unroll
     for (int i = 0; i < FR_NLD; ++i) {
         const int e = min(tid + 256 * i, NF * 16 - 1);
-        stg[i] = *reinterpret_cast<const float4*>(&src[(e >> 4) * C + (e & 15) * 4]);
+        stg[i] = cp::ld_f4<POL, S>(&src[(e >> 4) * C + (e & 15) * 4]);
     }
 }
 // same, from the attention kernel's head-major frame [4 heads][97][16]: channel c = head*16 + v
+template <int POL = 0, unsigned S = 0>
 __device__ __forceinline__ void frame_load_heads(const float* __restrict__ src, int tid, float4 (&stg)[FR_NLD]) {
 #pragma unroll
     for (int i = 0; i < FR_NLD; ++i) {
         const int e = min(tid + 256 * i, NF * 16 - 1);
-        stg[i] = *reinterpret_cast<const float4*>(&src[((e & 15) >> 2) * DV + (e >> 4) * VD + (e & 3) * 4]);
+        stg[i] = cp::ld_f4<POL, S>(&src[((e & 15) >> 2) * DV + (e >> 4) * VD + (e & 3) * 4]);
     }
 }
 __device__ __forceinline__ void frame_store(_Float16* ahi, _Float16* alo, int tid, const float4 (&stg)[FR_NLD]) {

@@ -61,20 +61,23 @@ def main(fetch_csv, write_csv, batch, out_json, sq_csv=None, sq2_csv=None, stats
     A = 15.52e6 * B
     qk = 5.82e6 * B
     wg = lambda nseq: ((nseq + 15) // 16) * 256          # LSTM launches: 16 sequences per 256-thread workgroup
-    # C-ABI call -> (kernel-name substring, grid size or None, algorithmic bytes per kernel launch)
+    # C-ABI call -> (kernel-name substring, grid size or None, algorithmic bytes per kernel launch[, name substring to leave out])
     table = {
         "lh_intra_block": (("k_intra_xp", "k_ln_lstm_lin"), None, 2.5 * A),
         "lh_inter_block": (("k_lstm_lin8", "k_inter_xp"), None, 2.0 * A),
         "lh_qkv_proj_ln": ("k_qkv_proj_ln", None, 2 * A + 2 * qk),
         "lh_local_attn": ("k_local_attn", None, 2 * qk + 2 * A),
-        "lh_proj_ln_res": ("k_proj_ln_res", None, 3 * A),
+        # the frame form reads merged and the residual and writes the frame; the tap-product form (second template argument true,
+        # the last block's) writes 36 tap products per (frame, bin) = 0.5625 A instead: two rows, or their average is neither's
+        "lh_proj_ln_res": ("k_proj_ln_res", None, 3 * A, "k_proj_ln_resILb0ELb1E"),
+        "lh_proj_ln_res_taps": ("k_proj_ln_resILb0ELb1E", None, 2.5625 * A),
         "lh_stft_conv_in": ("k_stft_conv_in", None, 16.16e6 * B),
         "lh_deconv_istft": ("k_deconv_istft", None, 16.16e6 * B),
     }
     kernels = {}
-    for call, (pat, grid, alg) in table.items():
+    for call, (pat, grid, alg, *skip) in table.items():
         pats = (pat,) if isinstance(pat, str) else pat
-        hit = lambda k: any(q in k[0] for q in pats) and (grid is None or k[1] == grid)
+        hit = lambda k: any(q in k[0] for q in pats) and not any(q in k[0] for q in skip) and (grid is None or k[1] == grid)
         f = [(k, v) for k, v in fe.items() if hit(k)]
         w = [(k, v) for k, v in wr.items() if hit(k)]
         if not f or not w:
