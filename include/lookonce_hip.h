@@ -521,6 +521,35 @@ int lh_render_moving(const float* src, const float* bank, const int* bank_of, co
                      const int* tgt_idx, float* events, unsigned* peak, float* mixture, float* target, int B, int S1, int N,
                      int Lh, int P, int K, int F, int frame, lh_stream_t stream);
 
+/* Moving sources at room length (ABI 27): lh_render_moving's definition — the same f, w, blend, gain, peak, mixture, target,
+ * clamping and refusals — with a and b_ computed by fp32 uniformly partitioned overlap-save instead of one fmaf chain each.
+ * The cross-fade is on the output side, so the whole response of path point f (and f + 1) applies to all past input of the
+ * outputs of frame f: nothing is approximated because the responses change.  The partitioning, integer arithmetic:
+ *     FZ = 1024 (transform size),  m = max(1, (FZ + 1 - frame) / frame),  Lp = m * frame  (frame + Lp - 1 <= FZ),
+ *     Q = ceil(Lh / Lp) partitions,  RING = (Q - 1) * m + 1 block spectra a frame looks back over,
+ *     RUN = max(25, 2 * (RING - 1)) frames per workgroup
+ *     block q = outputs [q frame, (q + 1) frame) = the last `frame` points of the inverse transform of
+ *               sum_{j < Q, q - j m >= 0} X[q - j m] . H[j],  j ascending, one fp32 fmaf order
+ *     X[q]    = transform of x[(q + 1) frame - FZ, (q + 1) frame), zeros outside [0, N)
+ *     H[p][j] = transform of (hL + i hR)[j Lp, (j + 1) Lp) of entry p, zero-padded, scaled by 1 / FZ (both ears in one transform)
+ * lh_bank_spectra writes the H of a whole bank; they depend on bank, Lh and frame only, so a caller with a fixed bank
+ * computes them once.
+ *   bank     [K][P][2][Lh]
+ *   spec     [K][P][Q][FZ] complex fp32 (K * P * Q * 8 KiB), 16-byte aligned: an opaque image (the bins are in the
+ *            transform's bit-reversed order) for lh_render_moving_fft with the same Lh and frame
+ *   work     scratch of lh_render_moving_fft, 16-byte aligned: unused (may be NULL) when RING <= 16; else
+ *            B * S1 * ceil(ceil(N / frame) / RUN) * RING * FZ complex fp32 (8 bytes each): the workgroups' block spectra
+ *   everything else as lh_render_moving.
+ * LH_ERR_ARG: as lh_render_moving, and a NULL or misaligned spec, or work where it is needed.  LH_ERR_UNSUPPORTED:
+ * frame % 8 != 0, frame > 512 (2 frame - 1 must fit the transform), Lh > 16384.  A refused call writes nothing.  No atomics in
+ * the convolution: bit-identical from call to call, row b does not depend on the other utterances, and a frame whose two path
+ * points name one entry has the bits of that entry alone.  Every events row is within (4e-6 max(1, sqrt(Lh / 256)) + 2^-21) of
+ * the float64 definition, relative to the row's largest |a|, |b_| times its gain (lh_render_moving's bound). */
+int lh_bank_spectra(const float* bank, float* spec, int K, int P, int Lh, int frame, lh_stream_t stream);
+int lh_render_moving_fft(const float* src, const float* spec, const int* bank_of, const int* idx, const float* gain,
+                         const int* tgt_idx, float* events, unsigned* peak, float* mixture, float* target, float* work, int B,
+                         int S1, int N, int Lh, int P, int K, int F, int frame, lh_stream_t stream);
+
 /* Eval metrics on the device (reference src/ts_hear_test.py:139-146, torchmetrics SI-SNR restated): per utterance
  * output_sisnr, si_snr_i (both averaged over the 2 channels) and cosine(embedding, embedding_gt); fp64 moments.
  *   outputs, target, mixture [B][2][n_samples]; emb, emb_gt [B][emb_dim]

@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -96,6 +96,9 @@ SIGNATURES = {
     # moving sources (ABI 24): bank lookup of a path and the time-varying FIR, BinauralRenderer.nearest / render_moving
     "lh_path_nearest": [_P] * 4 + [_I] * 5 + [_P],
     "lh_render_moving": [_P] * 10 + [_I] * 8 + [_P],
+    # ... at room length (ABI 27): the bank's partition spectra and the partitioned overlap-save form, render_moving(method="fft")
+    "lh_bank_spectra": [_P, _P, _I, _I, _I, _I, _P],
+    "lh_render_moving_fft": [_P] * 11 + [_I] * 8 + [_P],
     "lh_metric_sums": [_P] * 8 + [_I, _I, _I, _P],
     "lh_binaural_cues": [_P] * 5 + [_I, _I, _I, _I, c_double, _P],
     "lh_range_status": [_P, _P],

@@ -11,6 +11,7 @@
 //                  15-sample window of x in registers: 8 LDS reads and 8 scalar filter taps feed 64 FMAs.
 //   k_fft_conv     the same convolution by overlap-save FFT for 1024 <= Lh <= 4097 taps (BRIR-length responses)
 //   k_fir_moving   moving sources: two such chains per output, cross-faded between consecutive path points (lh_render_fft.hip)
+//   k_moving_fft   the same at room length: partitioned overlap-save over the bank's spectra, k_bank_spectra (lh_render_fft.hip)
 //   k_mix_peak     peak of |sum of sources| per utterance (order-independent: atomicMax on the float bit pattern)
 //   k_mix_apply    events / norm (when norm > 1), mixture = ((e0 + e1) + e2) + noise in the reference's order, target
 //   k_resample     polyphase sinc resampling of whole rows (the reference's last dataset step, torchaudio Resample, and its
@@ -110,6 +111,11 @@ int launch_fft_conv(const float* x, const float* h, const float* gain, float* y,
 // would spend the library's packed-fp32 budget (tests/test_cabi_symbols.py) twice.
 int launch_fir_moving(const float* x, const float* bank, const int* bank_of, const int* idx, const float* gain, float* y,
                       int rows, int S1, int N, int Lh, int P, int K, int F, int frame, hipStream_t st);
+// ... and so does their partitioned overlap-save form for room-length responses (k_bank_spectra, k_moving_fft)
+int moving_fft_supported(int Lh, int frame);
+bool moving_fft_needs_work(int Lh, int frame);
+int launch_moving_fft(const float* x, const float* spec, const int* bank_of, const int* idx, const float* gain, float* y,
+                      float* work, int rows, int S1, int N, int Lh, int P, int K, int F, int frame, hipStream_t st);
 
 // sum of the S1 rendered sources in the reference's order: ((e0 + e1) + ...) + noise (the last row)
 __device__ __forceinline__ float mix_sum(const float* __restrict__ ev, long stride, int S1, long i, float inv, bool scale) {
@@ -247,6 +253,28 @@ extern "C" int lh_render_moving(const float* src, const float* bank, const int* 
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(peak, 0, sizeof(unsigned) * B, st) != hipSuccess) return LH_ERR_LAUNCH;
     if (launch_fir_moving(src, bank, bank_of, idx, gain, events, B * S1, S1, N, Lh, P, K, F, frame, st) != LH_OK)
+        return LH_ERR_LAUNCH;
+    const int chunks = (int)((2L * N + 256 * 8 - 1) / (256 * 8));
+    hipLaunchKernelGGL(k_mix_peak, dim3(chunks, B), dim3(256), 0, st, events, peak, S1, N);
+    hipLaunchKernelGGL(k_mix_apply, dim3(chunks, B), dim3(256), 0, st, events, peak, tgt_idx, mixture, target, S1, N);
+    return check_launch();
+}
+
+// lh_render_moving with a and b_ from partitioned overlap-save over the bank's spectra (lh_bank_spectra; k_moving_fft in
+// lh_render_fft.hip); the blend, peak, mixture and target are lh_render_moving's.  A refused call writes nothing.
+extern "C" int lh_render_moving_fft(const float* src, const float* spec, const int* bank_of, const int* idx, const float* gain,
+                                    const int* tgt_idx, float* events, unsigned* peak, float* mixture, float* target, float* work,
+                                    int B, int S1, int N, int Lh, int P, int K, int F, int frame, lh_stream_t stream) {
+    using namespace lh;
+    if (!src || !spec || !bank_of || !idx || !gain || !tgt_idx || !events || !peak || !mixture || !target || B <= 0 || S1 <= 0 ||
+        N <= 0 || Lh <= 0 || P <= 0 || K <= 0 || F <= 0 || frame <= 0 || (long)B * S1 > 65535 || ((size_t)spec & 15))
+        return LH_ERR_ARG;
+    if (moving_fft_supported(Lh, frame) != LH_OK) return LH_ERR_UNSUPPORTED;
+    if ((long)F < ((long)N + frame - 1) / frame + 1) return LH_ERR_ARG;
+    if (moving_fft_needs_work(Lh, frame) && (!work || ((size_t)work & 15))) return LH_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(peak, 0, sizeof(unsigned) * B, st) != hipSuccess) return LH_ERR_LAUNCH;
+    if (launch_moving_fft(src, spec, bank_of, idx, gain, events, work, B * S1, S1, N, Lh, P, K, F, frame, st) != LH_OK)
         return LH_ERR_LAUNCH;
     const int chunks = (int)((2L * N + 256 * 8 - 1) / (256 * 8));
     hipLaunchKernelGGL(k_mix_peak, dim3(chunks, B), dim3(256), 0, st, events, peak, S1, N);

@@ -3,7 +3,8 @@
 // vectorisers.  Its complex multiplies become v_pk_mul_f32 / v_pk_fma_f32 with op_sel:[0,1] (src1's halves crossed)
 // under SLP — the one packed-fp32 form that returns wrong lanes 48..63 next to matrix-heavy kernels on this chip
 // (profiles/r03c_packed_fp32_corruption.txt, lookoncetohear_amd/build.py).
-// Below it: the moving-source renderer's two kernels, k_fir_moving and k_path_nearest (lh_render_moving, lh_path_nearest).
+// Below it: the moving-source renderer's kernels — k_fir_moving and k_path_nearest (lh_render_moving, lh_path_nearest), and the
+// partitioned overlap-save form for room-length responses, k_bank_spectra and k_moving_fft (lh_bank_spectra, lh_render_moving_fft).
 #include "lh_common.h"
 
 namespace lh {
@@ -259,6 +260,217 @@ int launch_fir_moving(const float* x, const float* bank, const int* bank_of, con
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Moving sources at room length (include/lookonce_hip.h, lh_bank_spectra / lh_render_moving_fft): the same definition as
+// k_fir_moving, with the two convolutions a and b_ computed by uniformly partitioned overlap-save.  The cross-fade is on the
+// OUTPUT side, so for the outputs of frame q the whole response of path point q (and q + 1) applies to all past input:
+//     block q = outputs [q frame, (q + 1) frame) = the last `frame` points of  ifft( sum_{j < Q, q - j m >= 0} X[q - j m] . H[e][j] )
+//     X[q]    = fft of x[(q + 1) frame - MF_Z, (q + 1) frame)                     (zeros outside [0, N); the row's alone)
+//     H[e][j] = fft of (hL + i hR)[j Lp, (j + 1) Lp) / MF_Z, zero-padded           (the bank's alone: lh_bank_spectra)
+//     m = max(1, (MF_Z + 1 - frame) / frame),  Lp = m frame  (frame + Lp - 1 <= MF_Z),  Q = ceil(Lh / Lp)
+// exact for responses that change from frame to frame: nothing is interpolated in the frequency domain.  As in k_fft_conv both
+// ears share one complex transform, the forward transform leaves bit-reversed order, the spectra are multiplied in that order
+// and the inverse takes it back; the 1 / MF_Z of the inverse is folded into H (a power of two: exact).
+//
+// k_moving_fft: a workgroup of 512 threads owns one row and a run of `run` consecutive frames.  It keeps the ring of the last
+// ring = (Q - 1) m + 1 block spectra in LDS when ring <= MF_LDS_RING (8 KiB each; 11 at frame 400 / Lh 4096), else in its own
+// slice of the caller's `work`, and recomputes the ring - 1 blocks in front of its run first (real input, not zeros).  Per frame:
+// all 512 threads transform the new block; then threads 0..255 run chain a and threads 256..511 chain b_ — sum over j ascending
+// in ONE fmaf order, each thread 4 bins as two 16-byte loads of X (LDS) and of H (global, re-read by every row: it is served by
+// the caches) — and each half inverts its own sum; a frame whose two path points name one entry leaves the second half idle
+// (workgroup-uniform; b_ - a would be exactly 0).  Both chains share every X.  No atomics; every output is written by one thread.
+// Radix-2 butterflies on float2 in LDS: stages with a span of at least 32 points are conflict-free (a half-wave reads one 256-byte
+// row), the five short-span stages are 2-way (two 128-byte runs of a half-wave fall on the same banks).
+// ------------------------------------------------------------------------------------------------------
+constexpr int MF_LOG = 10, MF_Z = 1 << MF_LOG;   // transform size
+constexpr int MF_LDS_RING = 16;                  // block spectra kept in LDS at most: (16 + 2) x 8 KiB + 4 KiB of the CU's 160 KiB
+constexpr int MF_RUN = 25;                       // frames per workgroup at least
+constexpr int MF_NT = 512;
+constexpr int MF_LH_MAX = 16384, MF_FRAME_MAX = 512;
+
+// 1024-point fft_dif / ifft_dit for NT threads (t < NT).  A thread with `on` false only keeps the barriers.
+template <int NT>
+__device__ __forceinline__ void fft_dif_z(float2* d, const float2* tw, int t, bool on) {
+    for (int lg = MF_LOG; lg >= 1; --lg) {
+        const int half = 1 << (lg - 1), ts = MF_LOG - lg;
+        if (on)
+            for (int k = t; k < MF_Z / 2; k += NT) {
+                const int j = k & (half - 1), a = ((k >> (lg - 1)) << lg) + j, b = a + half;
+                const float2 u = d[a], v = d[b];
+                d[a] = make_float2(u.x + v.x, u.y + v.y);
+                d[b] = cmul(make_float2(u.x - v.x, u.y - v.y), tw[j << ts]);
+            }
+        __syncthreads();
+    }
+}
+template <int NT>
+__device__ __forceinline__ void ifft_dit_z(float2* d, const float2* tw, int t, bool on) {
+    for (int lg = 1; lg <= MF_LOG; ++lg) {
+        const int half = 1 << (lg - 1), ts = MF_LOG - lg;
+        if (on)
+            for (int k = t; k < MF_Z / 2; k += NT) {
+                const int j = k & (half - 1), a = ((k >> (lg - 1)) << lg) + j, b = a + half;
+                const float2 u = d[a], v = cmulc(d[b], tw[j << ts]);
+                d[a] = make_float2(u.x + v.x, u.y + v.y);
+                d[b] = make_float2(u.x - v.x, u.y - v.y);
+            }
+        __syncthreads();
+    }
+}
+__device__ __forceinline__ void mf_twiddles(float2* tw, int tid, int nt) {
+    for (int k = tid; k < MF_Z / 2; k += nt) {
+        float sn, cs;
+        sincospif(-2.0f * (float)k / (float)MF_Z, &sn, &cs);
+        tw[k] = make_float2(cs, sn);
+    }
+}
+// acc += x . h on two complex bins; the order of the four fmaf per bin is the definition of the sum's bits
+__device__ __forceinline__ void mf_cmac(float4& acc, const float4 x, const float4 h) {
+    acc.x = fmaf(x.x, h.x, acc.x);
+    acc.x = fmaf(-x.y, h.y, acc.x);
+    acc.y = fmaf(x.x, h.y, acc.y);
+    acc.y = fmaf(x.y, h.x, acc.y);
+    acc.z = fmaf(x.z, h.z, acc.z);
+    acc.z = fmaf(-x.w, h.w, acc.z);
+    acc.w = fmaf(x.z, h.w, acc.w);
+    acc.w = fmaf(x.w, h.z, acc.w);
+}
+
+struct MfPlan {
+    int m, Lp, Q, ring, run;
+};
+// the partitioning of include/lookonce_hip.h; frame in [8, MF_FRAME_MAX], Lh in [1, MF_LH_MAX]
+inline MfPlan mf_plan(int Lh, int frame) {
+    MfPlan p;
+    p.m = (MF_Z + 1 - frame) / frame < 1 ? 1 : (MF_Z + 1 - frame) / frame;
+    p.Lp = p.m * frame;
+    p.Q = (Lh + p.Lp - 1) / p.Lp;
+    p.ring = (p.Q - 1) * p.m + 1;                                        // <= 2033
+    p.run = 2 * (p.ring - 1) > MF_RUN ? 2 * (p.ring - 1) : MF_RUN;
+    return p;
+}
+
+// grid (K P Q), block 256: spec[e][j] = fft_dif of (hL + i hR)[j Lp, (j + 1) Lp) / MF_Z of bank entry e = k P + p
+__global__ void __launch_bounds__(256) k_bank_spectra(const float* __restrict__ bank, float2* __restrict__ spec, int Lh, int Lp,
+                                                      int Q) {
+    __shared__ float2 d[MF_Z];
+    __shared__ float2 tw[MF_Z / 2];
+    const int tid = threadIdx.x;
+    const long e = blockIdx.x / Q;
+    const int j = blockIdx.x - (int)e * Q;
+    mf_twiddles(tw, tid, 256);
+    const float* hl = bank + e * 2 * Lh;
+    const int k0 = j * Lp, cnt = min(Lp, Lh - k0);
+    for (int i = tid; i < MF_Z; i += 256)
+        d[i] = i < cnt ? make_float2(hl[k0 + i] * (1.0f / MF_Z), hl[Lh + k0 + i] * (1.0f / MF_Z)) : make_float2(0.f, 0.f);
+    __syncthreads();
+    fft_dif_z<256>(d, tw, tid, true);
+    float2* out = spec + (long)blockIdx.x * MF_Z;
+    for (int i = tid; i < MF_Z; i += 256) out[i] = d[i];
+}
+
+// grid (ceil(ceil(N / frame) / run), B * S1), block 512, dynamic LDS: tw [512], buf [2][1024], then the ring [ring][1024]
+// (LDS_RING) or one staging block [1024].  x [B*S1][N], spec [K][P][Q][1024], idx [B*S1][F], y [B*S1][2][N],
+// work [B*S1][gridDim.x][ring][1024] (not LDS_RING)
+template <bool LDS_RING>
+__global__ void __launch_bounds__(MF_NT) k_moving_fft(const float* __restrict__ x, const float2* __restrict__ spec,
+                                                      const int* __restrict__ bank_of, const int* __restrict__ idx,
+                                                      const float* __restrict__ gain, float* __restrict__ y, float2* work, int S1,
+                                                      int N, int P, int K, int F, int frame, int m, int Q, int ring, int run) {
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float2* tw = reinterpret_cast<float2*>(lds4);
+    float2* buf = tw + MF_Z / 2;
+    float2* st = buf + 2 * MF_Z;
+    const int tid = threadIdx.x, row = blockIdx.y, c = tid >> 8, t = tid & 255;
+    const int nblk = (N + frame - 1) / frame;
+    const int q0 = blockIdx.x * run, q1 = min(q0 + run, nblk);
+    float2* rg = LDS_RING ? st : work + ((long)row * gridDim.x + blockIdx.x) * ring * MF_Z;
+    mf_twiddles(tw, tid, MF_NT);
+    // clamped when read: no argument of the C ABI can make the kernel read outside the image
+    const int bk = min(max(bank_of[row / S1], 0), K - 1);
+    const float* xr = x + (long)row * N;
+    const int* ir = idx + (long)row * F;
+    const float g = gain[row], fr = (float)frame;
+    float* yl = y + (long)row * 2 * N;
+    float2* mine = buf + c * MF_Z;
+    for (int q = max(0, q0 - (ring - 1)); q < q1; ++q) {
+        float2* slot = rg + (long)(q % ring) * MF_Z;
+        float2* d = LDS_RING ? slot : st;
+        // (the slot's last readers, block q - 1's sums, and the staging block's copy are behind a barrier)
+        const long lo = (long)(q + 1) * frame - MF_Z;
+        for (int i = tid; i < MF_Z; i += MF_NT) {
+            const long p = lo + i;
+            d[i] = make_float2((p >= 0 && p < N) ? xr[p] : 0.f, 0.f);
+        }
+        __syncthreads();
+        fft_dif_z<MF_NT>(d, tw, tid, true);
+        if (!LDS_RING) {
+            for (int i = tid; i < MF_Z; i += MF_NT) slot[i] = st[i];
+            __syncthreads();
+        }
+        if (q < q0) continue;                                            // a block in front of the run: its spectrum only
+        const int fa = min(q, F - 2);                                    // (q <= F - 2: the entry point checks F)
+        const int ia = min(max(ir[fa], 0), P - 1), ib = min(max(ir[fa + 1], 0), P - 1);
+        const bool two = ia != ib, on = c == 0 || two;
+        if (on) {
+            const float4* h = reinterpret_cast<const float4*>(spec + (((long)bk * P + (c ? ib : ia)) * Q) * MF_Z);
+            float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+            for (int j = 0; j < Q && q - j * m >= 0; ++j) {
+                const float4* xs = reinterpret_cast<const float4*>(rg + (long)((q - j * m) % ring) * MF_Z);
+                const float4* hj = h + (long)j * (MF_Z / 2);
+                mf_cmac(s0, xs[t], hj[t]);
+                mf_cmac(s1, xs[t + 256], hj[t + 256]);
+            }
+            reinterpret_cast<float4*>(mine)[t] = s0;
+            reinterpret_cast<float4*>(mine)[t + 256] = s1;
+        }
+        __syncthreads();
+        ifft_dit_z<256>(mine, tw, t, on);
+        for (int i = tid; i < frame; i += MF_NT) {
+            const long n = (long)q * frame + i;
+            if (n < N) {
+                const float2 a = buf[MF_Z - frame + i];
+                float l = a.x, r = a.y;
+                if (two) {
+                    const float2 b = buf[2 * MF_Z - frame + i];
+                    const float w = (float)i / fr;
+                    l = fmaf(w, b.x - a.x, a.x);
+                    r = fmaf(w, b.y - a.y, a.y);
+                }
+                yl[n] = l * g;
+                yl[N + n] = r * g;
+            }
+        }
+    }
+}
+
+// LH_OK, or LH_ERR_UNSUPPORTED for a frame or a length outside the partitioned path's range
+int moving_fft_supported(int Lh, int frame) {
+    return (frame % 8 || frame > MF_FRAME_MAX || Lh > MF_LH_MAX) ? LH_ERR_UNSUPPORTED : LH_OK;
+}
+bool moving_fft_needs_work(int Lh, int frame) { return mf_plan(Lh, frame).ring > MF_LDS_RING; }
+
+int launch_moving_fft(const float* x, const float* spec, const int* bank_of, const int* idx, const float* gain, float* y,
+                      float* work, int rows, int S1, int N, int Lh, int P, int K, int F, int frame, hipStream_t st) {
+    const MfPlan p = mf_plan(Lh, frame);
+    const int nblk = (N + frame - 1) / frame, runs = (nblk + p.run - 1) / p.run;
+    const float2* sp = reinterpret_cast<const float2*>(spec);
+    if (p.ring <= MF_LDS_RING) {
+        const int bytes = (int)sizeof(float2) * (MF_Z / 2 + 2 * MF_Z + p.ring * MF_Z);
+        if (bytes > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_moving_fft<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                bytes) != hipSuccess)
+            return LH_ERR_LAUNCH;
+        hipLaunchKernelGGL(k_moving_fft<true>, dim3(runs, rows), dim3(MF_NT), bytes, st, x, sp, bank_of, idx, gain, y,
+                           (float2*)nullptr, S1, N, P, K, F, frame, p.m, p.Q, p.ring, p.run);
+    } else {
+        const int bytes = (int)sizeof(float2) * (MF_Z / 2 + 2 * MF_Z + MF_Z);
+        hipLaunchKernelGGL(k_moving_fft<false>, dim3(runs, rows), dim3(MF_NT), bytes, st, x, sp, bank_of, idx, gain, y,
+                           reinterpret_cast<float2*>(work), S1, N, P, K, F, frame, p.m, p.Q, p.ring, p.run);
+    }
+    return check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // k_path_nearest: the bank lookup of the binding's `simulator_add_source(audio, path)` — for every path point v the bank
 // position (unit vectors; the scale of v does not matter) with the largest d_j = fmaf(v.z, p.z, fmaf(v.y, p.y, v.x p.x)),
 // the LOWEST such j (a strict > while scanning upward).  A zero vector gives 0; a non-finite point some index in [0, P).
@@ -295,6 +507,19 @@ __global__ void __launch_bounds__(256) k_path_nearest(const float* __restrict__ 
 }
 
 }  // namespace lh
+
+// The bank's partition spectra for lh_render_moving_fft (include/lookonce_hip.h): they depend on bank, Lh and frame only.
+extern "C" int lh_bank_spectra(const float* bank, float* spec, int K, int P, int Lh, int frame, lh_stream_t stream) {
+    using namespace lh;
+    if (!bank || !spec || ((size_t)spec & 15) || K <= 0 || P <= 0 || Lh <= 0 || frame <= 0) return LH_ERR_ARG;
+    if (moving_fft_supported(Lh, frame) != LH_OK) return LH_ERR_UNSUPPORTED;
+    const MfPlan p = mf_plan(Lh, frame);
+    const long blocks = (long)K * P * p.Q;
+    if (blocks > 0x7fffffffL) return LH_ERR_ARG;
+    hipLaunchKernelGGL(k_bank_spectra, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bank,
+                       reinterpret_cast<float2*>(spec), Lh, p.Lp, p.Q);
+    return check_launch();
+}
 
 // Bank lookup for lh_render_moving (include/lookonce_hip.h).
 extern "C" int lh_path_nearest(const float* paths, const float* positions, const int* bank_of, int* idx, int B, int S1, int F,

@@ -2,7 +2,7 @@
 launch stream; the entry points are called through the C ABI on preallocated buffers, so no host read sits between the events).
 
     python scripts/bench_render_moving.py [--out profiles/render_moving_cost.txt] [--batch 32] [--rows 4] [--n 80000]
-                                          [--lh 64,256,4096] [--steps 10] [--blocks 4] [--warmup 3]
+                                          [--lh 64,256,4096] [--steps 10] [--blocks 4] [--warmup 3] [--fft]
 
 Per response length: `lh_render_moving` (frame 400, a bank of 72 entries per utterance) interleaved in ONE run with
 `lh_render_binaural` on the same sources — blocks of `--steps` calls of each in turn, p50 per block; `scatter` is the spread of
@@ -11,6 +11,10 @@ in every frame) and `arcs` (synth's piecewise-arc law through `lh_path_nearest`:
 256 are direct form on both sides; at Lh = 4096 the static call takes its overlap-save FFT path and the moving one stays direct.
 `lh_path_nearest` is reported on its own (B x rows paths of 201 points against 1250 positions).  The operations are counted from
 the shapes: 2 x N x Lh x 2 ears per row and chain.
+`--fft` adds, in the SAME interleaved run, the partitioned overlap-save form `lh_render_moving_fft` on both kinds of path — with
+the bank's spectra computed before (`cached image`) and with `lh_bank_spectra` inside the timed call (`image in the call`) — and
+`lh_bank_spectra` alone; each is held against the direct moving call and the static call of that run
+(profiles/render_moving_fft_cost.txt: --fft --lh 256,512,1024,2048,4096,8192).
 """
 import argparse
 import os
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--fft", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_render_moving.py measures on an MI355X; no device found (there is no CPU path)")
@@ -99,6 +104,20 @@ def main():
         moving = lambda idx: (lambda: lib.call("lh_render_moving", D(src), D(bank), D(bank_of), D(idx), D(gain), D(tgt), D(ev), D(pk),
                                                D(mx), D(tg), B, S1, N, Lh, P, K, F, FRAME, st))
         arms = {"static": static, "moving, every frame": moving(every), "moving, arcs": moving(arcs)}
+        if args.fft:
+            from lookoncetohear_amd.render import FFT_LDS_RING, FFT_Z, fft_partition
+            _, _, Q, ring, run = fft_partition(Lh, FRAME)
+            spec = torch.empty(K, P, Q, FFT_Z, 2, device=dev)
+            runs = -(-(-(-N // FRAME)) // run)
+            work = torch.empty(B * S1 * runs * ring * FFT_Z, 2, device=dev) if ring > FFT_LDS_RING else None
+            image = lambda: lib.call("lh_bank_spectra", D(bank), D(spec), K, P, Lh, FRAME, st)
+            image()
+            fft = lambda idx: (lambda: lib.call("lh_render_moving_fft", D(src), D(spec), D(bank_of), D(idx), D(gain), D(tgt), D(ev),
+                                                D(pk), D(mx), D(tg), None if work is None else D(work), B, S1, N, Lh, P, K, F, FRAME, st))
+            both = lambda idx: (lambda f=fft(idx): (image(), f()))
+            arms.update({"fft, every frame, cached image": fft(every), "fft, arcs, cached image": fft(arcs),
+                         "fft, every frame, image in the call": both(every), "fft, arcs, image in the call": both(arcs),
+                         "lh_bank_spectra": image})
         for fn in arms.values():
             timed(fn, args.warmup, stream)
         ms = {k: [] for k in arms}
@@ -121,6 +140,19 @@ def main():
                 f"{1e3 * (max(p50s[k]) - min(p50s[k])):.1f} us) = {p50 / base:.2f} x static, difference {1e3 * (p50 - base):+.1f} us: "
                 f"{'WITHIN' if abs(p50 - base) <= 3 * scatter else 'NOT within'} three times the scatter; "
                 f"{chains * flop / p50 / 1e9:.1f} TFLOP/s over {chains:.2f} chains per output")
+        if args.fft:
+            say(f"    lh_bank_spectra ({K} x {P} entries x {Q} partitions, image {K * P * Q * FFT_Z * 8 / 2 ** 20:.1f} MiB"
+                f"{'' if work is None else f', scratch {work.numel() * 4 / 2 ** 20:.0f} MiB'}): p50 "
+                f"{statistics.median(ms['lh_bank_spectra']):.4f} ms")
+            for kind in ("every frame", "arcs"):
+                direct = statistics.median(ms[f"moving, {kind}"])
+                for how in ("cached image", "image in the call"):
+                    k = f"fft, {kind}, {how}"
+                    p50 = statistics.median(ms[k])
+                    say(f"    {k}: p50 {p50:.4f} ms (min {min(ms[k]):.4f}, max {max(ms[k]):.4f}, blocks' p50 spread "
+                        f"{1e3 * (max(p50s[k]) - min(p50s[k])):.1f} us) = {p50 / base:.2f} x static, {direct / p50:.2f} x faster than "
+                        f"the direct moving call ({1e3 * (direct - p50):+.1f} us): "
+                        f"{'FASTER' if direct - p50 > 3 * scatter else 'NOT faster'} by more than three times the scatter")
 
     Pn, Fn = 1250, 201
     posn = torch.nn.functional.normalize(torch.randn(K, Pn, 3, generator=g), dim=-1).to(dev)
