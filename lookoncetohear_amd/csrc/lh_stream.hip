@@ -217,14 +217,22 @@ __global__ void __launch_bounds__(IS_NT) k_inter_matvec(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Streaming sessions (include/lookonce_hip.h, ABI 16; row forms and moves: ABI 18): the first and the last node of a batched streamer's per-chunk graph.
+// Streaming sessions (include/lookonce_hip.h, ABI 16): the first and the last node of a batched streamer's per-chunk graph.
 // Slots (batch rows) open, close and fail one at a time while the chunk loop goes on in lock-step.  Plain streaming
 // kernels: a few word loads and the slot's 1.5 KB input row per wave to decide, 16-byte stores to zero a slot's state.
-// Who writes what: k_session_begin writes the gated input and the state it zeroes, never a word, so every workgroup of a
-// slot reaches the same decision from the same unmodified inputs; k_session_end (one workgroup per slot, after every other
-// kernel of the chunk) repeats that decision and is the only writer of cmd / active / fault.  A compacting host (ABI 18) has one
-// more writer, BEFORE both: k_session_move copies a moved row's `active` and device command word with the row, and the two
-// kernels then decide from the moved words.
+// One kernel per role — k_session_begin, k_session_end, k_session_move, k_session_capture — and two compile-time flags for
+// the forms a host can take; what a form does not have is not in its instantiation (if constexpr), not tested at run time:
+//   ROWS  (ABI 18) a compacting host: the words, the gated chunk and the state belong to ROW r, the input row, the output row,
+//         the hold word and the fault word to the listener's SLOT slot_of[r].  Without it row r is slot r.
+//   PACED (ABI 19) a listener whose chunk is late is HELD for the step instead of stalling the others.  hold[S] is one more
+//         input word per slot, posted by the host like the commands; pos[S] is the row's own K / V ring position and
+//         write_pos[S] what the chunk's kernels get of it.
+// Who writes what, in every form: every decision is a function of unmodified inputs (cmd, active, the input row; PACED:
+// hold).  k_session_begin writes the gated input, the state it zeroes and (PACED) write_pos, never a word, so every workgroup
+// of a row reaches the same decision; k_session_end (one workgroup per row, after every other kernel of the chunk) repeats
+// that decision and is the only writer of cmd / active / fault.  A compacting host has one more writer, BEFORE both:
+// k_session_move copies a moved row's `active`, device command word and (PACED) pos with the row, and the two kernels then
+// decide from the moved words.  lh_ring_advance_rows is the only other writer of pos.
 // ------------------------------------------------------------------------------------------------------
 struct SessSpans { lh_span_t s[LH_SESSION_MAX_SPANS]; int n; };     // travels in the kernel arguments
 constexpr int SS_NT = 256;
@@ -262,7 +270,8 @@ __device__ __forceinline__ SessLoads sess_load(const float* __restrict__ chunk_i
     return l;
 }
 // Wave-uniform, and the same in every wave of every workgroup of the chunk's two session kernels; every lane calls it.
-__device__ __forceinline__ SessDecision sess_decide(const SessLoads& l) {
+// A held row (PACED) is open and not consuming: live to the words, zeros to the separator, and never judged.
+__device__ __forceinline__ SessDecision sess_decide(const SessLoads& l, bool held) {
     SessDecision d;
     d.cmd = l.host | l.dev;
     d.gen = l.act;
@@ -274,51 +283,106 @@ __device__ __forceinline__ SessDecision sess_decide(const SessLoads& l) {
     }
     d.bad_in = wave_any(nonfinite4(l.x0) || nonfinite4(l.x1)) && d.gen != 0;      // an idle slot's input row is ignored
     d.live = d.gen != 0 && !d.bad_in;
+    if (held) d.bad_in = false, d.live = d.gen != 0;
     return d;
 }
-
-// grid (tiles, S), block 256
-__global__ void __launch_bounds__(SS_NT) k_session_begin(SessSpans sp, const float* __restrict__ chunk_in,
-                                                         float* __restrict__ chunk, const unsigned* __restrict__ cmd,
-                                                         const unsigned* __restrict__ active, int S) {
-    const int tid = threadIdx.x, s = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, s, tid & 63);
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long o = (long)s * SS_IN4 + min(tid, SS_IN4 - 1);
-    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[o];
-    const SessDecision d = sess_decide(l);
-    if (tile == 0 && tid < SS_IN4)                 // gate: only a live slot's samples reach the separator
-        reinterpret_cast<float4*>(chunk)[o] = d.live ? mine : z;
-    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
-    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the slot's slice of every state tensor
-        const long n16 = (long)(sp.s[i].bytes >> 4);
-        float4* p = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)s * sp.s[i].bytes);
-        const long hi = n16 * (tile + 1) / ntile;
-        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) p[j] = z;
+// ROWS: one more dependent load.  A row without a slot (< 0, or not a slot) decides as if the host had posted CLOSE: it is
+// idle whatever its words say, and a RESET the device posted on it is still served.
+struct SessRow { int slot; bool owned; };
+template <bool ROWS>
+__device__ __forceinline__ SessRow sess_row(const int* __restrict__ slot_of, int r, int S) {
+    if constexpr (ROWS) {
+        const int slot = slot_of[r];
+        const bool owned = slot >= 0 && slot < S;
+        return SessRow{owned ? slot : 0, owned};
+    } else {
+        return SessRow{r, true};
     }
 }
 
-// grid S, block 1024.  One workgroup per slot scans the slot's output row and fresh (h, c): 150 KB.  Every thread requests its
-// share of up to SE_SP spans in one go (SE_U float4 per span: 2048 cover a 97 x 64 state row) before it looks at any of them —
-// a loop that waited for each load took 26 us per chunk (profiles/r08a_sessions_cost.txt).
-constexpr int SE_NT = 1024, SE_SP = LH_SESSION_MAX_END_SPANS, SE_U = 2;
-__global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, const float* __restrict__ chunk_in, float* out,
-                                                       unsigned* cmd, unsigned* active, unsigned* fault, int S) {
-    __shared__ int wbad[SE_NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, s = blockIdx.x;
-    const SessLoads l = sess_load(chunk_in, cmd, active, S, s, s, lane);
+// grid (tiles, rows launched), block 256; the words keep their stride S.  PACED: tile 0 writes write_pos[row]: -1 for a held
+// or non-live row (lh_qkv_proj_ln_rows then writes no K / V row), 0 for a row that serves a RESET, pos[row] otherwise.  A held
+// row's commands are served: a RESET zeroes its state here, and the chunk's kernels still run, on the zero-gated input.
+template <bool ROWS, bool PACED>
+__global__ void __launch_bounds__(SS_NT) k_session_begin(SessSpans sp, const float* __restrict__ chunk_in,
+                                                         float* __restrict__ chunk, const unsigned* __restrict__ cmd,
+                                                         const unsigned* __restrict__ active, const int* __restrict__ slot_of,
+                                                         const unsigned* __restrict__ hold, const int* __restrict__ pos,
+                                                         int* __restrict__ write_pos, int S) {
+    const int tid = threadIdx.x, r = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
+    const SessRow w = sess_row<ROWS>(slot_of, r, S);
+    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, tid & 63);
+    unsigned h = 0u;
+    int p = 0;
+    if constexpr (PACED) h = hold[w.slot], p = pos[r];
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4* o4 = reinterpret_cast<float4*>(out) + (long)s * SS_OUT4;
-    const float4 ov = o4[tid & (SS_OUT4 - 1)];
+    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[(long)w.slot * SS_IN4 + min(tid, SS_IN4 - 1)];
+    if (!w.owned) l.host = LH_SESSION_CLOSE;
+    const bool held = PACED && w.owned && h != 0u;
+    const SessDecision d = sess_decide(l, held);
+    const bool takes = d.live && !held;            // the row consumes this chunk
+    if (tile == 0) {
+        if (tid < SS_IN4)                          // gather and gate: only a live listener's samples reach the separator
+            reinterpret_cast<float4*>(chunk)[(long)r * SS_IN4 + tid] = takes ? mine : z;
+        if constexpr (PACED)
+            if (tid == 0) write_pos[r] = !takes ? -1 : (d.cmd & LH_SESSION_RESET) ? 0 : p;
+    }
+    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
+    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the row's slice of every state tensor
+        const long n16 = (long)(sp.s[i].bytes >> 4);
+        float4* q = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)r * sp.s[i].bytes);
+        const long hi = n16 * (tile + 1) / ntile;
+        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) q[j] = z;
+    }
+}
+
+// grid rows launched (+ 1 with ROWS), block 1024.  One workgroup per row scans the row's output and fresh (h, c), sp: 150 KB.
+// Every thread requests its share of up to SE_SP spans in one go (SE_U float4 per span: 2048 cover a 97 x 64 state row) before
+// it looks at any of them — a loop that waited for each load took 26 us per chunk (profiles/r08a_sessions_cost.txt).
+// ROWS: the workgroup scatters the row's output, or zeros, to out[slot_of[r]], reports under the SLOT's number and takes the
+// row's entry out of the move table; the workgroup after the last row silences every slot that has no row among those
+// launched, so every row of `out` is written in every chunk.  Without ROWS there is one output buffer, `out`.
+// PACED: a held row is never judged, neither its input row nor what the kernels made of the zeros.  Their output is thrown
+// away, and the row's slice of every tensor of the ping-pong set the chunk READ is copied over the set it WROTE (cp.s[2 i] the
+// tensor read, cp.s[2 i + 1] the one written in its place; bytes; the rings and pos were never touched), so after the step
+// the row is, bit for bit, what it was before.  CLOSE is served as ever; a RESET that begin served (the carried state is then
+// the zeros) is posted again for as long as the row is held, so that the chunk that takes the listener's first samples still
+// finds it and starts the ring at 0.
+constexpr int SE_NT = 1024, SE_SP = LH_SESSION_MAX_END_SPANS, SE_U = 2, SM_U = 4;
+template <bool ROWS, bool PACED>
+__global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, SessSpans cp, const float* __restrict__ chunk_in,
+                                                       const float* __restrict__ out_rows, float* __restrict__ out,
+                                                       unsigned* cmd, unsigned* active, unsigned* fault,
+                                                       const unsigned* __restrict__ hold,
+                                                       const int* __restrict__ slot_of, const int* __restrict__ row_of,
+                                                       int* from, int n_rows, int S) {
+    __shared__ int wbad[SE_NT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, r = blockIdx.x;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (ROWS) {
+        if (r >= n_rows) {                         // the whole workgroup: 16 slots of 64 float4 per pass
+            for (int q = tid >> 6; q < S; q += SE_NT / 64) {
+                const int qr = row_of[q];
+                if (qr < 0 || qr >= n_rows) reinterpret_cast<float4*>(out)[(long)q * SS_OUT4 + lane] = z;
+            }
+            return;
+        }
+    }
+    const SessRow w = sess_row<ROWS>(slot_of, r, S);
+    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, lane);
+    unsigned h = 0u;
+    if constexpr (PACED) h = hold[w.slot];
+    // without ROWS there is one output buffer, scanned in place: out_rows is `out` or nothing, and never dereferenced
+    const float4 ov = reinterpret_cast<const float4*>(ROWS ? out_rows : out)[(long)r * SS_OUT4 + (tid & (SS_OUT4 - 1))];
     // branch-free: a span the table does not have is span 0 again, an index past the end is the last one (re-reading is free)
     float4 v[SE_SP][SE_U];
 #pragma unroll
     for (int i = 0; i < SE_SP; ++i) {
         const lh_span_t sq = sp.s[i < sp.n ? i : 0];
         const int last = (int)min((long)(sq.bytes >> 4), (long)SE_U * SE_NT) - 1;
-        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)s * sq.bytes);
+        const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)r * sq.bytes);
 #pragma unroll
-        for (int u = 0; u < SE_U; ++u) v[i][u] = p[min(tid + u * SE_NT, last)];
+        for (int u = 0; u < SE_U; ++u) v[i][u] = q[min(tid + u * SE_NT, last)];
     }
     bool bad = nonfinite4(ov);
 #pragma unroll
@@ -327,128 +391,65 @@ __global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, const float
         for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
     for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
         const long n16 = (long)(sp.s[i].bytes >> 4);
-        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
-                                                          (unsigned long long)s * sp.s[i].bytes);
-        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(p[j]);
-    }
-    const SessDecision d = sess_decide(l);
-    bad = wave_any(bad);
-    if (lane == 0) wbad[tid >> 6] = bad ? 1 : 0;
-    __syncthreads();                               // also: every wave has read the words thread 0 is about to write
-    int any = 0;
-#pragma unroll
-    for (int w = 0; w < SE_NT / 64; ++w) any |= wbad[w];
-    // a true fp32 overflow from finite input: non-finite output or fresh (h, c) of a live slot
-    const bool overflow = d.live && any != 0;
-    const bool on = d.live && !overflow;
-    if (!on && tid < SS_OUT4) o4[tid] = z;
-    if (tid == 0) {
-        active[s] = on ? d.gen : 0u;
-        // pinned host memory the host reads in place: plain stores at system scope, like the range flag (lh_backend.hip)
-        if (d.bad_in || overflow) __hip_atomic_store(&fault[s], d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[s], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        cmd[s] = 0u;
-        cmd[S + s] = overflow ? (unsigned)LH_SESSION_RESET : 0u;
-    }
-}
-
-// Row forms (ABI 18): the words, the gated chunk and the state belong to ROW r of a compacting host, the input row to the
-// listener's SLOT slot_of[r].  A row without a slot (< 0, or not a slot) decides as if the host had posted CLOSE: it is idle
-// whatever its words say, and a RESET the device posted on it is still served.
-struct SessRow { int slot; bool owned; };
-__device__ __forceinline__ SessRow sess_row(const int* __restrict__ slot_of, int r, int S) {
-    const int slot = slot_of[r];
-    const bool owned = slot >= 0 && slot < S;
-    return SessRow{owned ? slot : 0, owned};
-}
-
-// grid (tiles, rows launched), block 256; the words keep their stride S.  k_session_begin with one more dependent load
-__global__ void __launch_bounds__(SS_NT) k_session_begin_rows(SessSpans sp, const float* __restrict__ chunk_in,
-                                                              float* __restrict__ chunk, const unsigned* __restrict__ cmd,
-                                                              const unsigned* __restrict__ active,
-                                                              const int* __restrict__ slot_of, int S) {
-    const int tid = threadIdx.x, r = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const SessRow w = sess_row(slot_of, r, S);
-    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, tid & 63);
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[(long)w.slot * SS_IN4 + min(tid, SS_IN4 - 1)];
-    if (!w.owned) l.host = LH_SESSION_CLOSE;
-    const SessDecision d = sess_decide(l);
-    if (tile == 0 && tid < SS_IN4)                 // gather and gate: chunk[row] = chunk_in[slot] of a live listener
-        reinterpret_cast<float4*>(chunk)[(long)r * SS_IN4 + tid] = d.live ? mine : z;
-    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
-    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the row's slice of every state tensor
-        const long n16 = (long)(sp.s[i].bytes >> 4);
-        float4* p = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)r * sp.s[i].bytes);
-        const long hi = n16 * (tile + 1) / ntile;
-        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) p[j] = z;
-    }
-}
-
-// grid rows launched + 1, block 1024.  Workgroup r < n_rows is ROW r: k_session_end's scan of the row's output and fresh
-// (h, c), then it scatters the row's output, or zeros, to out[slot_of[r]], reports under the SLOT's number and takes the
-// row's entry out of the move table.  The workgroup after the last row silences every slot that has no row among those
-// launched, so every row of `out` is written in every chunk.
-__global__ void __launch_bounds__(SE_NT) k_session_end_rows(SessSpans sp, const float* __restrict__ chunk_in,
-                                                            const float* __restrict__ out_rows, float* __restrict__ out,
-                                                            unsigned* cmd, unsigned* active, unsigned* fault,
-                                                            const int* __restrict__ slot_of, const int* __restrict__ row_of,
-                                                            int* from, int n_rows, int S) {
-    __shared__ int wbad[SE_NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, r = blockIdx.x;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r >= n_rows) {                             // the whole workgroup: 16 slots of 64 float4 per pass
-        for (int q = tid >> 6; q < S; q += SE_NT / 64) {
-            const int qr = row_of[q];
-            if (qr < 0 || qr >= n_rows) reinterpret_cast<float4*>(out)[(long)q * SS_OUT4 + lane] = z;
-        }
-        return;
-    }
-    const SessRow w = sess_row(slot_of, r, S);
-    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, lane);
-    const float4 ov = reinterpret_cast<const float4*>(out_rows)[(long)r * SS_OUT4 + (tid & (SS_OUT4 - 1))];
-    float4 v[SE_SP][SE_U];                         // branch-free, all requested before any is looked at (k_session_end)
-#pragma unroll
-    for (int i = 0; i < SE_SP; ++i) {
-        const lh_span_t sq = sp.s[i < sp.n ? i : 0];
-        const int last = (int)min((long)(sq.bytes >> 4), (long)SE_U * SE_NT) - 1;
-        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)r * sq.bytes);
-#pragma unroll
-        for (int u = 0; u < SE_U; ++u) v[i][u] = p[min(tid + u * SE_NT, last)];
-    }
-    bool bad = nonfinite4(ov);
-#pragma unroll
-    for (int i = 0; i < SE_SP; ++i)
-#pragma unroll
-        for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
-    for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
-        const long n16 = (long)(sp.s[i].bytes >> 4);
-        const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
+        const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
                                                           (unsigned long long)r * sp.s[i].bytes);
-        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(p[j]);
+        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(q[j]);
     }
     if (!w.owned) l.host = LH_SESSION_CLOSE;
-    const SessDecision d = sess_decide(l);
+    const bool held = PACED && w.owned && h != 0u;           // uniform over the workgroup
+    if constexpr (PACED) {
+        if (held) {
+            // carry: what the chunk's kernels wrote from the zeros is overwritten with what the row had.  A thread's SM_U loads
+            // are requested together; thread t only ever touches elements t + k SE_NT, the ones it scanned above
+            for (int i = 0; i + 1 < cp.n; i += 2) {
+                const long n16 = (long)(cp.s[i].bytes >> 4);
+                const unsigned long long off = (unsigned long long)r * cp.s[i].bytes;
+                const float4* ps = reinterpret_cast<const float4*>(static_cast<const char*>(cp.s[i].base) + off);
+                float4* pd = reinterpret_cast<float4*>(static_cast<char*>(cp.s[i + 1].base) + off);
+                for (long j = tid; j < n16; j += (long)SM_U * SE_NT) {
+                    float4 c[SM_U];
+#pragma unroll
+                    for (int u = 0; u < SM_U; ++u) c[u] = ps[min(j + (long)u * SE_NT, n16 - 1)];
+#pragma unroll
+                    for (int u = 0; u < SM_U; ++u)
+                        if (j + (long)u * SE_NT < n16) pd[j + (long)u * SE_NT] = c[u];
+                }
+            }
+        }
+    }
+    const SessDecision d = sess_decide(l, held);
     bad = wave_any(bad);
     if (lane == 0) wbad[tid >> 6] = bad ? 1 : 0;
     __syncthreads();                               // also: every wave has read the words thread 0 is about to write
     int any = 0;
 #pragma unroll
     for (int q = 0; q < SE_NT / 64; ++q) any |= wbad[q];
-    const bool overflow = d.live && any != 0;
+    // a true fp32 overflow from finite input: non-finite output or fresh (h, c) of a live row.  A held row's scan has no verdict
+    const bool overflow = d.live && !held && any != 0;
     const bool on = d.live && !overflow;
-    if (w.owned && tid < SS_OUT4) reinterpret_cast<float4*>(out)[(long)w.slot * SS_OUT4 + tid] = on ? ov : z;
+    const bool sounds = on && !held;
+    // Every form keeps the store to `out` it had.  A row that does not sound is silenced in all of them.  The row form also
+    // scatters a sounding row to its slot, in every chunk; the paced forms, which a slot host gives out_rows == out, do so
+    // unless that would copy the row onto itself; the lock-step form never has to
+    const bool scatter = PACED ? out_rows != out : ROWS;
+    if (w.owned && tid < SS_OUT4 && (!sounds || scatter))
+        reinterpret_cast<float4*>(out)[(long)w.slot * SS_OUT4 + tid] = sounds ? ov : z;
     if (tid == 0) {
         active[r] = on ? d.gen : 0u;
-        if (w.owned) {                             // an unowned row is idle: nothing to report
+        // pinned host memory the host reads in place: plain stores at system scope, like the range flag (lh_backend.hip).
+        // An unowned row is idle: nothing to report
+        if (w.owned) {
             if (d.bad_in || overflow) __hip_atomic_store(&fault[w.slot], d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[w.slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         cmd[r] = 0u;
-        cmd[S + r] = overflow ? (unsigned)LH_SESSION_RESET : 0u;
-        if (from) from[r] = 0;
+        // held through its RESET: the row's first consumed chunk must still see it (ring position 0)
+        cmd[S + r] = (overflow || (held && on && (d.cmd & LH_SESSION_RESET))) ? (unsigned)LH_SESSION_RESET : 0u;
+        if constexpr (ROWS || PACED)
+            if (from) from[r] = 0;
     }
 }
+
 
 // Row moves (ABI 18): the first node of a compacting host's chunk.  from[d] = r + 1 copies row r over row d — the row's slice
 // of every span (the state of lh_session_begin's table and the speaker gain), its `active` word and the command word the
@@ -457,16 +458,20 @@ __global__ void __launch_bounds__(SE_NT) k_session_end_rows(SessSpans sp, const 
 // host hands out disjoint pairs (every source lies above, every destination below the new row count), so the workgroups of
 // one launch share nothing; a row without an entry costs its workgroups one word load.  lh_session_end_rows zeroes the
 // entries afterwards: the table is read-only here, and a replay without a new table moves nothing.
-constexpr int SM_U = 4;
+// PACED: the row's ring position goes with it.
+template <bool PACED>
 __global__ void __launch_bounds__(SS_NT) k_session_move(SessSpans sp, const int* __restrict__ from, unsigned* cmd,
-                                                        unsigned* active, int S) {
+                                                        unsigned* active, int* pos, int S) {
     const int tid = threadIdx.x, dst = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
     const int src = from[dst] - 1;
     if (src < 0 || src >= S || src == dst) return;
     if (tile == 0 && tid == 0) {
         const unsigned a = active[src], c = cmd[S + src];
+        int p = 0;
+        if constexpr (PACED) p = pos[src];
         active[dst] = a;
         cmd[S + dst] = c;
+        if constexpr (PACED) pos[dst] = p;
     }
     for (int i = 0; i < sp.n; ++i) {
         const long n16 = (long)(sp.s[i].bytes >> 4);
@@ -493,13 +498,17 @@ __global__ void __launch_bounds__(SS_NT) k_session_move(SessSpans sp, const int*
 // The clip is read by stream-ordered work only (the host enqueues the embedder behind an event it records after it has seen
 // the done word), so the done word needs no release: it tells the host WHICH chunk finished the clip, not that the bytes
 // are visible to the host.
+// PACED: a held slot's commands are served, its row is neither recorded nor judged.
 constexpr int SC_NT = 64;
 static_assert(NMIC * HOP / 4 == SC_NT && HOP / 4 == 32, "one float4 per lane: lane = 32 channel + float4 of the channel");
+template <bool PACED>
 __global__ void __launch_bounds__(SC_NT) k_session_capture(const float* __restrict__ chunk_in, float* __restrict__ enroll,
-                                                           unsigned* ecmd, unsigned* estate, unsigned* edone, int n_chunks,
-                                                           int S) {
+                                                           unsigned* ecmd, unsigned* estate, unsigned* edone,
+                                                           const unsigned* __restrict__ hold, int n_chunks, int S) {
     const int s = blockIdx.x, lane = threadIdx.x, ch = lane >> 5, q = lane & 31;
     const unsigned cmd = ecmd[s];
+    unsigned held = 0u;
+    if constexpr (PACED) held = hold[s];
     unsigned gen = estate[s], k = estate[S + s];
     const float4 v = reinterpret_cast<const float4*>(chunk_in + ((long)s * NMIC + ch) * NFFT)[q];
     if (cmd & LH_ENROLL_CANCEL) gen = 0u;
@@ -508,9 +517,10 @@ __global__ void __launch_bounds__(SC_NT) k_session_capture(const float* __restri
         if (gen == 0u) gen = 1u;
         k = 0u;
     }
-    if (cmd == 0u && gen == 0u) return;            // wave-uniform: an idle slot with nothing posted costs the loads above
+    // wave-uniform: an idle (or held) slot with nothing posted costs the loads above
+    if (cmd == 0u && (gen == 0u || held != 0u)) return;
     unsigned done = 0u;
-    if (gen != 0u) {
+    if (gen != 0u && held == 0u) {
         if (wave_any(nonfinite4(v))) {
             done = gen | LH_ENROLL_FAULT;
         } else {
@@ -525,212 +535,6 @@ __global__ void __launch_bounds__(SC_NT) k_session_capture(const float* __restri
         estate[s] = gen;
         estate[S + s] = k;
         // pinned host memory the host reads in place, like fault[S]
-        if (done != 0u) __hip_atomic_store(&edone[s], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Paced sessions (ABI 19): a listener whose chunk is late is HELD for the step instead of stalling the others.  hold[S] is
-// one more input word per SLOT (the row forms look it up through slot_of), posted by the host like the commands; pos[S] is
-// the row's own K / V ring position and write_pos[S] what the chunk's kernels get of it.  Who writes what, as above: every
-// decision is a function of unmodified inputs (cmd, active, hold, the input row).  Tile 0 of k_session_begin_paced writes
-// write_pos[row]: -1 for a held or non-live row (lh_qkv_proj_ln_rows then writes no K / V row), 0 for a row that serves a
-// RESET, pos[row] otherwise; lh_ring_advance_rows is the only writer of pos (k_session_move_paced copies it with the row);
-// k_session_end_paced stays the only writer of the words.  A held row's kernels still run, on the zero-gated input: the end
-// kernel throws their output away and copies the row's slice of every tensor of the ping-pong set the chunk READ over the set
-// it WROTE (bytes; the rings and pos were never touched), so after the step the row is, bit for bit, what it was before.
-// A held row is never judged: neither its input row nor what the kernels made of the zeros.  Its commands are served: CLOSE
-// as ever; a RESET is served by begin (the carried state is then the zeros) and posted again by end for as long as the row
-// is held, so that the chunk that takes the listener's first samples still finds it and starts the ring at 0.
-// One kernel each for the slot forms (slot_of == NULL: row r is slot r) and the row forms.
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ SessRow sess_row_or_slot(const int* __restrict__ slot_of, int r, int S) {
-    return slot_of ? sess_row(slot_of, r, S) : SessRow{r, true};
-}
-__device__ __forceinline__ SessDecision sess_decide_paced(const SessLoads& l, bool held) {
-    SessDecision d = sess_decide(l);
-    if (held) d.bad_in = false, d.live = d.gen != 0;      // open and not consuming: live to the words, zeros to the separator
-    return d;
-}
-
-// grid (tiles, rows launched), block 256
-__global__ void __launch_bounds__(SS_NT) k_session_begin_paced(SessSpans sp, const float* __restrict__ chunk_in,
-                                                               float* __restrict__ chunk, const unsigned* __restrict__ cmd,
-                                                               const unsigned* __restrict__ active,
-                                                               const int* __restrict__ slot_of,
-                                                               const unsigned* __restrict__ hold, const int* __restrict__ pos,
-                                                               int* __restrict__ write_pos, int S) {
-    const int tid = threadIdx.x, r = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const SessRow w = sess_row_or_slot(slot_of, r, S);
-    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, tid & 63);
-    const unsigned h = hold[w.slot];
-    const int p = pos[r];
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 mine = reinterpret_cast<const float4*>(chunk_in)[(long)w.slot * SS_IN4 + min(tid, SS_IN4 - 1)];
-    if (!w.owned) l.host = LH_SESSION_CLOSE;
-    const bool held = w.owned && h != 0u;
-    const SessDecision d = sess_decide_paced(l, held);
-    const bool takes = d.live && !held;            // the row consumes this chunk
-    if (tile == 0) {
-        if (tid < SS_IN4) reinterpret_cast<float4*>(chunk)[(long)r * SS_IN4 + tid] = takes ? mine : z;
-        if (tid == 0) write_pos[r] = !takes ? -1 : (d.cmd & LH_SESSION_RESET) ? 0 : p;
-    }
-    if (!(d.cmd & LH_SESSION_RESET) && !d.bad_in) return;
-    for (int i = 0; i < sp.n; ++i) {               // this tile's share of the row's slice of every state tensor
-        const long n16 = (long)(sp.s[i].bytes >> 4);
-        float4* q = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)r * sp.s[i].bytes);
-        const long hi = n16 * (tile + 1) / ntile;
-        for (long j = n16 * tile / ntile + tid; j < hi; j += SS_NT) q[j] = z;
-    }
-}
-
-// grid rows launched (+ 1 in the row form: k_session_end_rows' last workgroup), block 1024.  sp: the (h, c) just written, as in
-// k_session_end; cp: the carry table, cp.s[2 i] the tensor the chunk read, cp.s[2 i + 1] the one it wrote in its place.
-__global__ void __launch_bounds__(SE_NT) k_session_end_paced(SessSpans sp, SessSpans cp, const float* __restrict__ chunk_in,
-                                                             const float* out_rows, float* out, unsigned* cmd,
-                                                             unsigned* active, unsigned* fault,
-                                                             const unsigned* __restrict__ hold,
-                                                             const int* __restrict__ slot_of, const int* __restrict__ row_of,
-                                                             int* from, int n_rows, int S) {
-    __shared__ int wbad[SE_NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, r = blockIdx.x;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r >= n_rows) {                             // row form only: slots without a row among those launched
-        for (int q = tid >> 6; q < S; q += SE_NT / 64) {
-            const int qr = row_of[q];
-            if (qr < 0 || qr >= n_rows) reinterpret_cast<float4*>(out)[(long)q * SS_OUT4 + lane] = z;
-        }
-        return;
-    }
-    const SessRow w = sess_row_or_slot(slot_of, r, S);
-    SessLoads l = sess_load(chunk_in, cmd, active, S, r, w.slot, lane);
-    const unsigned h = hold[w.slot];
-    const float4 ov = reinterpret_cast<const float4*>(out_rows)[(long)r * SS_OUT4 + (tid & (SS_OUT4 - 1))];
-    float4 v[SE_SP][SE_U];                         // branch-free, all requested before any is looked at (k_session_end)
-#pragma unroll
-    for (int i = 0; i < SE_SP; ++i) {
-        const lh_span_t sq = sp.s[i < sp.n ? i : 0];
-        const int last = (int)min((long)(sq.bytes >> 4), (long)SE_U * SE_NT) - 1;
-        const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)r * sq.bytes);
-#pragma unroll
-        for (int u = 0; u < SE_U; ++u) v[i][u] = q[min(tid + u * SE_NT, last)];
-    }
-    bool bad = nonfinite4(ov);
-#pragma unroll
-    for (int i = 0; i < SE_SP; ++i)
-#pragma unroll
-        for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
-    for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
-        const long n16 = (long)(sp.s[i].bytes >> 4);
-        const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
-                                                          (unsigned long long)r * sp.s[i].bytes);
-        for (long j = tid + (long)SE_U * SE_NT; j < n16; j += SE_NT) bad |= nonfinite4(q[j]);
-    }
-    if (!w.owned) l.host = LH_SESSION_CLOSE;
-    const bool held = w.owned && h != 0u;          // uniform over the workgroup
-    if (held) {
-        // carry: what the chunk's kernels wrote from the zeros is overwritten with what the row had.  A thread's SM_U loads
-        // are requested together; thread t only ever touches elements t + k SE_NT, the ones it scanned above
-        for (int i = 0; i + 1 < cp.n; i += 2) {
-            const long n16 = (long)(cp.s[i].bytes >> 4);
-            const unsigned long long off = (unsigned long long)r * cp.s[i].bytes;
-            const float4* ps = reinterpret_cast<const float4*>(static_cast<const char*>(cp.s[i].base) + off);
-            float4* pd = reinterpret_cast<float4*>(static_cast<char*>(cp.s[i + 1].base) + off);
-            for (long j = tid; j < n16; j += (long)SM_U * SE_NT) {
-                float4 c[SM_U];
-#pragma unroll
-                for (int u = 0; u < SM_U; ++u) c[u] = ps[min(j + (long)u * SE_NT, n16 - 1)];
-#pragma unroll
-                for (int u = 0; u < SM_U; ++u)
-                    if (j + (long)u * SE_NT < n16) pd[j + (long)u * SE_NT] = c[u];
-            }
-        }
-    }
-    const SessDecision d = sess_decide_paced(l, held);
-    bad = wave_any(bad);
-    if (lane == 0) wbad[tid >> 6] = bad ? 1 : 0;
-    __syncthreads();                               // also: every wave has read the words thread 0 is about to write
-    int any = 0;
-#pragma unroll
-    for (int q = 0; q < SE_NT / 64; ++q) any |= wbad[q];
-    const bool overflow = d.live && !held && any != 0;      // a held row's scan has no verdict
-    const bool on = d.live && !overflow;
-    const bool sounds = on && !held;
-    if (w.owned && tid < SS_OUT4 && (!sounds || out_rows != out))
-        reinterpret_cast<float4*>(out)[(long)w.slot * SS_OUT4 + tid] = sounds ? ov : z;
-    if (tid == 0) {
-        active[r] = on ? d.gen : 0u;
-        if (w.owned) {
-            if (d.bad_in || overflow) __hip_atomic_store(&fault[w.slot], d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            else if (d.cmd & LH_SESSION_OPEN) __hip_atomic_store(&fault[w.slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        cmd[r] = 0u;
-        // held through its RESET: the row's first consumed chunk must still see it (ring position 0)
-        cmd[S + r] = (overflow || (held && on && (d.cmd & LH_SESSION_RESET))) ? (unsigned)LH_SESSION_RESET : 0u;
-        if (from) from[r] = 0;
-    }
-}
-
-// k_session_move, and the row's ring position with it
-__global__ void __launch_bounds__(SS_NT) k_session_move_paced(SessSpans sp, const int* __restrict__ from, unsigned* cmd,
-                                                              unsigned* active, int* pos, int S) {
-    const int tid = threadIdx.x, dst = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const int src = from[dst] - 1;
-    if (src < 0 || src >= S || src == dst) return;
-    if (tile == 0 && tid == 0) {
-        const unsigned a = active[src], c = cmd[S + src];
-        const int p = pos[src];
-        active[dst] = a;
-        cmd[S + dst] = c;
-        pos[dst] = p;
-    }
-    for (int i = 0; i < sp.n; ++i) {
-        const long n16 = (long)(sp.s[i].bytes >> 4);
-        const float4* ps = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
-                                                           (unsigned long long)src * sp.s[i].bytes);
-        float4* pd = reinterpret_cast<float4*>(static_cast<char*>(sp.s[i].base) + (unsigned long long)dst * sp.s[i].bytes);
-        const long hi = n16 * (tile + 1) / ntile;
-        for (long j = n16 * tile / ntile + tid; j < hi; j += (long)SM_U * SS_NT) {
-            float4 v[SM_U];
-#pragma unroll
-            for (int u = 0; u < SM_U; ++u) v[u] = ps[min(j + (long)u * SS_NT, hi - 1)];
-#pragma unroll
-            for (int u = 0; u < SM_U; ++u)
-                if (j + (long)u * SS_NT < hi) pd[j + (long)u * SS_NT] = v[u];
-        }
-    }
-}
-
-// k_session_capture for a paced host: a held slot's commands are served, its row is neither recorded nor judged
-__global__ void __launch_bounds__(SC_NT) k_session_capture_paced(const float* __restrict__ chunk_in, float* __restrict__ enroll,
-                                                                 unsigned* ecmd, unsigned* estate, unsigned* edone,
-                                                                 const unsigned* __restrict__ hold, int n_chunks, int S) {
-    const int s = blockIdx.x, lane = threadIdx.x, ch = lane >> 5, q = lane & 31;
-    const unsigned cmd = ecmd[s], held = hold[s];
-    unsigned gen = estate[s], k = estate[S + s];
-    const float4 v = reinterpret_cast<const float4*>(chunk_in + ((long)s * NMIC + ch) * NFFT)[q];
-    if (cmd & LH_ENROLL_CANCEL) gen = 0u;
-    if (cmd & LH_ENROLL_ARM) {
-        gen = (cmd >> LH_ENROLL_GEN_SHIFT) & 0x7fffffu;
-        if (gen == 0u) gen = 1u;
-        k = 0u;
-    }
-    if (cmd == 0u && (gen == 0u || held != 0u)) return;      // wave-uniform: nothing posted, nothing to record
-    unsigned done = 0u;
-    if (gen != 0u && held == 0u) {
-        if (wave_any(nonfinite4(v))) {
-            done = gen | LH_ENROLL_FAULT;
-        } else {
-            k = min(k, (unsigned)n_chunks - 1u);
-            reinterpret_cast<float4*>(enroll + ((long)s * NMIC + ch) * HOP * n_chunks + (long)HOP * k)[q] = v;
-            if (++k == (unsigned)n_chunks) done = gen;
-        }
-    }
-    if (done != 0u || gen == 0u) gen = 0u, k = 0u;
-    if (lane == 0) {
-        if (cmd != 0u) ecmd[s] = 0u;
-        estate[s] = gen;
-        estate[S + s] = k;
         if (done != 0u) __hip_atomic_store(&edone[s], done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -815,10 +619,11 @@ __device__ __forceinline__ int snap_wrap(int p, int window) {      // any word -
     return p < 0 ? p + window : p;
 }
 
-// grid (SNAP_TILES, n_flat + n_rings + 1), block 256
-__global__ void __launch_bounds__(SNAP_NT) k_session_save(SnapLayout L, const float4* __restrict__ embed, char* __restrict__ snap,
-                                                          const unsigned* __restrict__ cmd, const unsigned* __restrict__ active,
-                                                          const int* __restrict__ pos, int row, int S) {
+// One listener's sections over blockIdx (tile, section): row `row` of the buffers -> `snap`.  `embed` is the listener's own
+// embedding, `pos` the word that holds the row's position.
+__device__ __forceinline__ void snap_save(const SnapLayout& L, int row, const float4* __restrict__ embed, char* __restrict__ snap,
+                                          const unsigned* __restrict__ cmd, const unsigned* __restrict__ active,
+                                          const int* __restrict__ pos, int S) {
     const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
     const int nf = L.flat.n, nr = L.rings.n;
     if (q < nf) {
@@ -846,11 +651,11 @@ __global__ void __launch_bounds__(SNAP_NT) k_session_save(SnapLayout L, const fl
         }
     }
 }
-
-// grid (SNAP_TILES, n_flat + n_rings + 1), block 256.  Exactly one of pos_row / pos_shared.
-__global__ void __launch_bounds__(SNAP_NT) k_session_restore(SnapLayout L, float4* __restrict__ embed, const char* __restrict__ snap,
-                                                             unsigned* cmd, int* pos_row, const int* __restrict__ pos_shared,
-                                                             unsigned* fault, unsigned gen, int row, int S) {
+// The way back: `snap` -> row `row`, the listener's embedding, cmd[1][row] and, in a paced host, the row's position word
+// `pos_row` (else NULL: the rings are rotated to the shared counter).  `fault` is the slot's own word.
+__device__ __forceinline__ void snap_restore(const SnapLayout& L, int row, float4* __restrict__ embed, const char* __restrict__ snap,
+                                             unsigned* cmd, int* pos_row, const int* __restrict__ pos_shared, unsigned* fault,
+                                             unsigned gen, int S) {
     const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
     const int nf = L.flat.n, nr = L.rings.n;
     const unsigned* words = reinterpret_cast<const unsigned*>(snap + SNAP_WORDS);
@@ -884,6 +689,19 @@ __global__ void __launch_bounds__(SNAP_NT) k_session_restore(SnapLayout L, float
     }
 }
 
+// grid (SNAP_TILES, n_flat + n_rings + 1), block 256
+__global__ void __launch_bounds__(SNAP_NT) k_session_save(SnapLayout L, const float4* __restrict__ embed, char* __restrict__ snap,
+                                                          const unsigned* __restrict__ cmd, const unsigned* __restrict__ active,
+                                                          const int* __restrict__ pos, int row, int S) {
+    snap_save(L, row, embed, snap, cmd, active, pos, S);
+}
+// grid (SNAP_TILES, n_flat + n_rings + 1), block 256.  Exactly one of pos_row / pos_shared.
+__global__ void __launch_bounds__(SNAP_NT) k_session_restore(SnapLayout L, float4* __restrict__ embed, const char* __restrict__ snap,
+                                                             unsigned* cmd, int* pos_row, const int* __restrict__ pos_shared,
+                                                             unsigned* fault, unsigned gen, int row, int S) {
+    snap_restore(L, row, embed, snap, cmd, pos_row, pos_shared, fault, gen, S);
+}
+
 // Suspend / resume of many listeners (ABI 21): the two kernels above with the listener as a third grid dimension and a table in
 // device memory that says, per item, which row, whose slot, which snapshot of a [.][stride] buffer.  The same sections, the same
 // copy (snap_copy, the layout helpers), the same words; embed, fault and the position words are BASES here, indexed by slot,
@@ -903,80 +721,22 @@ __global__ void __launch_bounds__(SNAP_NT) k_session_save_rows(SnapLayout L, con
                                                                const unsigned* __restrict__ active,
                                                                const int* __restrict__ pos_rows, const int* __restrict__ pos_shared,
                                                                const lh_snap_item_t* __restrict__ items, int S) {
-    const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const int nf = L.flat.n, nr = L.rings.n;
     const SnapItem it = snap_item(items, blockIdx.z, S);
     if (!it.ok) return;
-    const int row = it.row;
-    char* snap = snaps + (unsigned long long)it.index * stride;
-    if (q < nf) {
-        const lh_span_t sq = L.flat.s[q];
-        snap_copy(reinterpret_cast<const float4*>(static_cast<const char*>(sq.base) + (unsigned long long)row * sq.bytes),
-                  reinterpret_cast<float4*>(snap + snap_offset(L, q)), (long)(sq.bytes >> 4), tile, ntile, tid, SnapDense{},
-                  SnapDense{});
-    } else if (q < nf + nr) {
-        const int i = q - nf;
-        const SnapRing ring = snap_ring(L, i, 0u);
-        const float4* src = reinterpret_cast<const float4*>(L.rings.s[i].base) + (long)row * L.heads * ring.head_stride;
-        snap_copy(src, reinterpret_cast<float4*>(snap + snap_offset(L, q)), (long)L.heads * ring.per_head, tile, ntile, tid, ring,
-                  SnapDense{});
-    } else if (tile == 0) {
-        const unsigned a = active[row], c = cmd[S + row];
-        const int p = pos_rows ? pos_rows[row] : pos_shared[0];
-        const int e16 = (int)(L.embed_bytes >> 4);
-        const float4* se = reinterpret_cast<const float4*>(embed + (unsigned long long)it.slot * L.embed_bytes);
-        float4* pe = reinterpret_cast<float4*>(snap + SNAP_EMBED);
-        for (int j = tid; j < e16; j += SNAP_NT) pe[j] = se[j];
-        if (tid == 0) {
-            unsigned* hw = reinterpret_cast<unsigned*>(snap);
-            for (int w = 0; w < LH_SNAPSHOT_HEADER_BYTES / 4; ++w) hw[w] = snap_header_word(L, w);
-            hw += SNAP_WORDS / 4;
-            hw[0] = a, hw[1] = c, hw[2] = (unsigned)snap_wrap(p, L.window), hw[3] = 0u;
-        }
-    }
+    snap_save(L, it.row, reinterpret_cast<const float4*>(embed + (unsigned long long)it.slot * L.embed_bytes),
+              snaps + (unsigned long long)it.index * stride, cmd, active, pos_rows ? pos_rows + it.row : pos_shared, S);
 }
-
-// grid (tiles, n_flat + n_rings + 1, n_items), block 256.  Exactly one of pos_rows / pos_shared.
+// grid (tiles, n_flat + n_rings + 1, n_items), block 256.  Exactly one of pos_rows / pos_shared; every item is rotated by its
+// own delta, from its own saved position.
 __global__ void __launch_bounds__(SNAP_NT) k_session_restore_rows(SnapLayout L, char* __restrict__ embed,
                                                                   const char* __restrict__ snaps, unsigned long long stride,
                                                                   unsigned* cmd, int* pos_rows, const int* __restrict__ pos_shared,
                                                                   unsigned* fault, const lh_snap_item_t* __restrict__ items, int S) {
-    const int tid = threadIdx.x, q = blockIdx.y, tile = blockIdx.x, ntile = gridDim.x;
-    const int nf = L.flat.n, nr = L.rings.n;
     const SnapItem it = snap_item(items, blockIdx.z, S);
     if (!it.ok) return;
-    const int row = it.row;
-    const char* snap = snaps + (unsigned long long)it.index * stride;
-    const unsigned* words = reinterpret_cast<const unsigned*>(snap + SNAP_WORDS);
-    const unsigned was_active = words[0], was_cmd = words[1];
-    const int saved = snap_wrap((int)words[2], L.window);
-    if (q < nf) {
-        const lh_span_t sq = L.flat.s[q];
-        snap_copy(reinterpret_cast<const float4*>(snap + snap_offset(L, q)),
-                  reinterpret_cast<float4*>(static_cast<char*>(sq.base) + (unsigned long long)row * sq.bytes),
-                  (long)(sq.bytes >> 4), tile, ntile, tid, SnapDense{}, SnapDense{});
-    } else if (q < nf + nr) {
-        const int i = q - nf;
-        // a lock-step target: every item is rotated by its own delta, from its own saved position
-        const int delta = pos_shared ? snap_wrap(snap_wrap(pos_shared[0], L.window) - saved, L.window) : 0;
-        const SnapRing ring = snap_ring(L, i, (unsigned)delta);
-        float4* dst = reinterpret_cast<float4*>(L.rings.s[i].base) + (long)row * L.heads * ring.head_stride;
-        snap_copy(reinterpret_cast<const float4*>(snap + snap_offset(L, q)), dst, (long)L.heads * ring.per_head, tile, ntile, tid,
-                  SnapDense{}, ring);
-    } else if (tile == 0) {
-        const int e16 = (int)(L.embed_bytes >> 4);
-        const float4* pe = reinterpret_cast<const float4*>(snap + SNAP_EMBED);
-        float4* de = reinterpret_cast<float4*>(embed + (unsigned long long)it.slot * L.embed_bytes);
-        for (int j = tid; j < e16; j += SNAP_NT) de[j] = pe[j];
-        if (tid == 0) {
-            cmd[S + row] = was_cmd;
-            if (pos_rows) pos_rows[row] = saved;
-            if (was_active == 0u) {                   // a dead snapshot stays dead, as in k_session_restore
-                cmd[row] = (unsigned)(LH_SESSION_CLOSE | LH_SESSION_RESET);
-                __hip_atomic_store(&fault[it.slot], it.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
+    snap_restore(L, it.row, reinterpret_cast<float4*>(embed + (unsigned long long)it.slot * L.embed_bytes),
+                 snaps + (unsigned long long)it.index * stride, cmd, pos_rows ? pos_rows + it.row : nullptr, pos_shared,
+                 fault + it.slot, it.gen, S);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1190,6 +950,10 @@ static bool sess_spans(const lh_span_t* spans, int n_spans, SessSpans& sp) {
     sp.n = n_spans;
     return true;
 }
+// Tiles of the begin and move kernels per row launched.  ~10 MB of state per slot, mostly rings: enough tiles that one RESET is
+// microseconds (64 workgroups zero a slot in ~13 us), few enough that the idle launch of a large batch stays a handful of
+// early-out workgroups per CU
+static int sess_tiles(int n) { return n <= 16 ? 64 : (n >= 64 ? 16 : 1024 / n); }
 }  // namespace lh
 
 extern "C" int lh_session_begin(const lh_span_t* spans, int n_spans, const float* chunk_in, float* chunk, const unsigned* cmd,
@@ -1198,11 +962,9 @@ extern "C" int lh_session_begin(const lh_span_t* spans, int n_spans, const float
     SessSpans sp;
     if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || S <= 0 || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    // ~10 MB of state per slot, mostly rings: enough tiles that one RESET is microseconds (64 workgroups zero a slot in ~13 us),
-    // few enough that the idle launch of a large batch stays a handful of early-out workgroups per CU
-    const int tiles = S <= 16 ? 64 : (S >= 64 ? 16 : 1024 / S);
-    hipLaunchKernelGGL(k_session_begin, dim3(tiles, S), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in, chunk, cmd, active,
-                       S);
+    hipLaunchKernelGGL((k_session_begin<false, false>), dim3(sess_tiles(S), S), dim3(SS_NT), 0, (hipStream_t)stream, sp,
+                       chunk_in, chunk, cmd, active, (const int*)nullptr, (const unsigned*)nullptr, (const int*)nullptr,
+                       (int*)nullptr, S);
     return check_launch();
 }
 
@@ -1212,21 +974,19 @@ extern "C" int lh_session_end(const lh_span_t* spans, int n_spans, const float* 
     SessSpans sp;
     if (!chunk_in || !out || !cmd || !active || !fault || S <= 0 || n_spans > SE_SP || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_end, dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, chunk_in, out, cmd, active, fault, S);
+    hipLaunchKernelGGL((k_session_end<false, false>), dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, SessSpans{}, chunk_in,
+                       (const float*)out, out, cmd, active, fault, (const unsigned*)nullptr, (const int*)nullptr,
+                       (const int*)nullptr, (int*)nullptr, S, S);
     return check_launch();
 }
-
-namespace lh {
-static int sess_tiles(int n) { return n <= 16 ? 64 : (n >= 64 ? 16 : 1024 / n); }     // as lh_session_begin, per row launched
-}  // namespace lh
 
 extern "C" int lh_session_move(const lh_span_t* spans, int n_spans, const int* from, unsigned* cmd, unsigned* active, int n_rows,
                                int S, lh_stream_t stream) {
     using namespace lh;
     SessSpans sp;
     if (!from || !cmd || !active || S <= 0 || n_rows < 1 || n_rows > S || !sess_spans(spans, n_spans, sp)) return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_move, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, from, cmd,
-                       active, S);
+    hipLaunchKernelGGL((k_session_move<false>), dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, from,
+                       cmd, active, (int*)nullptr, S);
     return check_launch();
 }
 
@@ -1238,8 +998,8 @@ extern "C" int lh_session_begin_rows(const lh_span_t* spans, int n_spans, const 
     if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || !slot_of || S <= 0 || n_rows < 1 || n_rows > S ||
         !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_begin_rows, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in,
-                       chunk, cmd, active, slot_of, S);
+    hipLaunchKernelGGL((k_session_begin<true, false>), dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp,
+                       chunk_in, chunk, cmd, active, slot_of, (const unsigned*)nullptr, (const int*)nullptr, (int*)nullptr, S);
     return check_launch();
 }
 
@@ -1251,8 +1011,8 @@ extern "C" int lh_session_end_rows(const lh_span_t* spans, int n_spans, const fl
     if (!chunk_in || !out_rows || !out || out_rows == out || !cmd || !active || !fault || !slot_of || !row_of || S <= 0 ||
         n_rows < 1 || n_rows > S || n_spans > SE_SP || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_end_rows, dim3(n_rows + 1), dim3(SE_NT), 0, (hipStream_t)stream, sp, chunk_in, out_rows, out,
-                       cmd, active, fault, slot_of, row_of, from, n_rows, S);
+    hipLaunchKernelGGL((k_session_end<true, false>), dim3(n_rows + 1), dim3(SE_NT), 0, (hipStream_t)stream, sp, SessSpans{},
+                       chunk_in, out_rows, out, cmd, active, fault, (const unsigned*)nullptr, slot_of, row_of, from, n_rows, S);
     return check_launch();
 }
 
@@ -1261,8 +1021,8 @@ extern "C" int lh_session_capture(const float* chunk_in, float* enroll, unsigned
     using namespace lh;
     if (!chunk_in || !enroll || !ecmd || !estate || !edone || S <= 0 || n_chunks < 1) return LH_ERR_ARG;
     if (((unsigned long long)(size_t)enroll & 15) || ((unsigned long long)(size_t)chunk_in & 15)) return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_capture, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate, edone,
-                       n_chunks, S);
+    hipLaunchKernelGGL((k_session_capture<false>), dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate,
+                       edone, (const unsigned*)nullptr, n_chunks, S);
     return check_launch();
 }
 
@@ -1285,8 +1045,8 @@ extern "C" int lh_session_begin_paced(const lh_span_t* spans, int n_spans, const
     if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || !hold || !pos || !write_pos || pos == write_pos ||
         S <= 0 || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_begin_paced, dim3(sess_tiles(S), S), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in, chunk,
-                       cmd, active, (const int*)nullptr, hold, pos, write_pos, S);
+    hipLaunchKernelGGL((k_session_begin<false, true>), dim3(sess_tiles(S), S), dim3(SS_NT), 0, (hipStream_t)stream, sp, chunk_in,
+                       chunk, cmd, active, (const int*)nullptr, hold, pos, write_pos, S);
     return check_launch();
 }
 
@@ -1299,7 +1059,7 @@ extern "C" int lh_session_begin_rows_paced(const lh_span_t* spans, int n_spans, 
     if (!chunk_in || !chunk || chunk_in == chunk || !cmd || !active || !slot_of || !hold || !pos || !write_pos ||
         pos == write_pos || S <= 0 || n_rows < 1 || n_rows > S || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_begin_paced, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp,
+    hipLaunchKernelGGL((k_session_begin<true, true>), dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp,
                        chunk_in, chunk, cmd, active, slot_of, hold, pos, write_pos, S);
     return check_launch();
 }
@@ -1312,8 +1072,8 @@ extern "C" int lh_session_end_paced(const lh_span_t* spans, int n_spans, const l
     if (!chunk_in || !out || !cmd || !active || !fault || !hold || S <= 0 || n_spans > SE_SP || !sess_spans(spans, n_spans, sp) ||
         !sess_pairs(carry, n_pairs, cp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_end_paced, dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, cp, chunk_in, (const float*)out,
-                       out, cmd, active, fault, hold, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, S, S);
+    hipLaunchKernelGGL((k_session_end<false, true>), dim3(S), dim3(SE_NT), 0, (hipStream_t)stream, sp, cp, chunk_in,
+                       (const float*)out, out, cmd, active, fault, hold, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, S, S);
     return check_launch();
 }
 
@@ -1327,8 +1087,8 @@ extern "C" int lh_session_end_rows_paced(const lh_span_t* spans, int n_spans, co
         S <= 0 || n_rows < 1 || n_rows > S || n_spans > SE_SP || !sess_spans(spans, n_spans, sp) ||
         !sess_pairs(carry, n_pairs, cp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_end_paced, dim3(n_rows + 1), dim3(SE_NT), 0, (hipStream_t)stream, sp, cp, chunk_in, out_rows,
-                       out, cmd, active, fault, hold, slot_of, row_of, from, n_rows, S);
+    hipLaunchKernelGGL((k_session_end<true, true>), dim3(n_rows + 1), dim3(SE_NT), 0, (hipStream_t)stream, sp, cp, chunk_in,
+                       out_rows, out, cmd, active, fault, hold, slot_of, row_of, from, n_rows, S);
     return check_launch();
 }
 
@@ -1338,7 +1098,7 @@ extern "C" int lh_session_move_paced(const lh_span_t* spans, int n_spans, const 
     SessSpans sp;
     if (!from || !cmd || !active || !pos || S <= 0 || n_rows < 1 || n_rows > S || !sess_spans(spans, n_spans, sp))
         return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_move_paced, dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, from,
+    hipLaunchKernelGGL((k_session_move<true>), dim3(sess_tiles(n_rows), n_rows), dim3(SS_NT), 0, (hipStream_t)stream, sp, from,
                        cmd, active, pos, S);
     return check_launch();
 }
@@ -1348,7 +1108,7 @@ extern "C" int lh_session_capture_paced(const float* chunk_in, float* enroll, un
     using namespace lh;
     if (!chunk_in || !enroll || !ecmd || !estate || !edone || !hold || S <= 0 || n_chunks < 1) return LH_ERR_ARG;
     if (((unsigned long long)(size_t)enroll & 15) || ((unsigned long long)(size_t)chunk_in & 15)) return LH_ERR_ARG;
-    hipLaunchKernelGGL(k_session_capture_paced, dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate,
+    hipLaunchKernelGGL((k_session_capture<true>), dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, enroll, ecmd, estate,
                        edone, hold, n_chunks, S);
     return check_launch();
 }
