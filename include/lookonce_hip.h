@@ -73,14 +73,14 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (26); bumped on any signature change. */
+/* ABI version of this header (28); bumped on any signature change. */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
  * intra LSTM, key 1 = same for the inter LSTM, key 2 = fused intra kernel (0 = k_intra_xp, the hand-ordered
  * software-pipelined step; 2 = the previous k_ln_lstm_lin), key 3 = 0 switches off the issue-priority de-phasing of
  * the two workgroups that share a CU in k_ln_lstm_lin (default on), key 4 = query frames per attention workgroup
- * (1 / 2 = tiles of 16, 3 = 40 frames in three tiles; 0 = automatic), key 5 = fused inter kernel (0 = k_inter_xp,
+ * (1 / 2 = tiles of 16, 3 = 40 frames in three tiles, 5 = 79 frames in five; 0 = automatic; 4 is refused), key 5 = fused inter kernel (0 = k_inter_xp,
  * the hand-ordered step with per-phase issue priority; 2 = the previous k_lstm_lin8p), key 6 = runs of consecutive tiles per utterance in
  * lh_deconv_istft (0 = automatic: 256 / B), key 7 = bytes of dynamic LDS added to k_intra_xp launches (timing probe:
  * one workgroup per CU), key 8 = issue priority in k_intra_xp (0 = none, 1 = static priority for the odd wave slot of a SIMD: default, 2 / 3 =
@@ -93,6 +93,11 @@ int lh_abi_version(void);
  * lh_qkv_proj_ln_rows and the one-tile attention shape (clips of at most 16 frames, or key 4 = 1) are streaming paths and run
  * plain accesses under every value; outputs do not depend on the key; other values: LH_ERR_ARG. */
 int lh_set_tuning(int key, int value);
+
+/* Query frames per attention workgroup (16, 32, 40 or 79) that lh_local_attn / lh_local_attn_win use for a whole clip of
+ * T frames at batch B under the current key 4: *frames (a host word).  A time window whose t0 is a multiple of it is cut
+ * into the tiles of the whole-clip launch, and its outputs are then the whole-clip launch's bit for bit. */
+int lh_attn_tile_frames(int B, int T, int* frames);
 
 /* Validates model_params (reference net.py:21-49 / configs/tsh.json:5-19) against the compiled constants. */
 int lh_check_config(int nfft, int hop, int n_mics, int emb_dim, int n_blocks_unused, int lstm_hidden,

@@ -11,7 +11,7 @@ from ctypes import c_double, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -21,6 +21,7 @@ SIGNATURES = {
     "lh_stft_conv_in": [_P] * 7 + [_I] * 3 + [_P],
     "lh_embed_proj_ln": [_P] * 7 + [_I, _P],
     "lh_set_tuning": [_I, _I],
+    "lh_attn_tile_frames": [_I, _I, _P],
     "lh_ln_lstm_intra": [_P] * 6 + [_I, _I, _P],
     "lh_ln_lstm_inter": [_P] * 10 + [_I, _I, _I, _P],
     "lh_intra_stream": [_P] * 5 + [_I, _P],

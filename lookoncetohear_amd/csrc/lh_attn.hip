@@ -8,8 +8,8 @@
 // order the v_mfma_f32_16x16x32_f16 operands want, lh_common.h), so both contractions run as three fp16 MFMAs per tile
 // (hi*hi + hi*lo + lo*hi into one accumulator, ~22 mantissa bits) with no conversion work in this kernel:
 //   * scores  S = Q K^T: banded tile products (query tile mq x key tiles mq..mq+4), the 19 feature k-steps split
-//     over the 4 waves, partial sums reduced through LDS; A and B fragments are 32-byte row segments straight from
-//     global memory (two-deep register ring);
+//     over the 4 waves, partial sums reduced through LDS (79-frame tiles: whole products per wave, no partial sums);
+//     A and B fragments are 32-byte row segments straight from global memory (two-deep register ring);
 //   * softmax over exactly the 50 in-window slots (zero history rows take part, no mask — reference behaviour),
 //     P written to LDS as fp16 hi/lo rows;
 //   * O = P V: per 32-key step a lane loads the [hi 4 | lo 4] quads of 8 key rows for its 4 columns (256-byte row
@@ -30,8 +30,6 @@ struct Frag { f16x8 h, l; };               // 8 k-values of one operand row: hi 
 struct VQuad { f16x4 h, l; };              // one key row, 4 columns
 
 constexpr int AT_KSTEPS = (DQKP + 31) / 32;   // 19 feature k-steps of 32
-constexpr int AT_PKS = 3;                     // 32-key steps in P.V (96 >= 32 + 49)
-constexpr int AT_PP = AT_PKS * 32 + 8;        // P row stride in halves (208 bytes: conflict-free ds_read_b128)
 constexpr int AT_CG = (DV + 63) / 64;         // 25 column groups of 64 V columns
 
 #if defined(LH_PROBE_TRACE)               // timing probe build only (scripts/probe_trace.py): workgroup 803, wave 0
@@ -45,16 +43,30 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                                                        const _Float16* __restrict__ vx, float* __restrict__ merged,
                                                        int BH, int T, int ntt, int tw0, int tend) {
     // TQ query frames per workgroup in MQ MFMA row tiles (TQ = 16 MQ, or 40 in 3 tiles: 625 frames are then 16 tiles
-    // per (batch, head), 2048 workgroups at batch 32 = exactly four rounds of the 512 resident workgroups)
-    constexpr int NKEYS = TQ + HIST;           // key rows they can see (65 / 81 / 89)
-    constexpr int NKT = (NKEYS + 15) / 16;     // key tiles in the score phase (5 / 6)
+    // per (batch, head), 2048 workgroups at batch 32 = exactly four rounds of the 512 resident workgroups; or 79 in 5
+    // tiles: 8 tiles per (batch, head), two rounds — attn_form below)
+    constexpr int NKEYS = TQ + HIST;           // key rows they can see (65 / 81 / 89 / 128)
+    constexpr int NKT = (NKEYS + 15) / 16;     // key tiles in the score phase (5 / 6 / 8)
     constexpr int NK = NKT * 16;
     constexpr int ND = 5;                      // key tiles per query tile: nt = mq .. mq+4 (as far as they exist)
     constexpr int NB = ND * 16;                // band width stored per query row
-    static_assert(TQ <= 16 * MQ && TQ > 16 * (MQ - 1) && NKEYS <= AT_PKS * 32 && NK - 1 <= HIST + KV_PAD, "tile geometry");
-    __shared__ float sp[4][TQ][NB];            // per-wave partial scores, band-relative columns (d, l15)
-    __shared__ __attribute__((aligned(16))) _Float16 ph[16 * MQ][AT_PP];
-    __shared__ __attribute__((aligned(16))) _Float16 pl[16 * MQ][AT_PP];
+    constexpr int PKS = (NKEYS + 31) / 32;     // 32-key steps in P.V (3; 79-frame tiles: 128 keys = exactly 4)
+    constexpr int PP = PKS * 32 + 8;           // P row stride in halves (208 / 272 bytes: conflict-free ds_read_b128)
+    // OWN (79-frame tiles, MQ = 5): a wave owns whole tile products over all 19 k-steps — the five of query tile `wave` and
+    // product (4, 4 + wave) of the band's 24 — instead of every product over a quarter of the k-steps.  No partial sums:
+    // `sp` is one copy (25 KB; four copies of an 80 x 80 band would be 102 KB), and 69 KB of LDS keep two workgroups per CU.
+    constexpr bool OWN = MQ > 4;
+    // OWN reads 128 key rows, 30 more than the pad rows cover behind a tile that starts at the clip's last frame.  A tile whose
+    // rows 96..127 would lie behind the buffer (t0 > T - 31) has fewer than 31 frames, and keys 96..127 belong to queries 47..78
+    // only: it reads rows 64..95 a second time in their place (KBACK) — scores nobody uses, and P is exactly 0 there.
+    constexpr int KBACK = OWN ? 32 : 0;
+    static_assert(TQ <= 16 * MQ && TQ > 16 * (MQ - 1) && NK - 1 - KBACK <= HIST + KV_PAD, "tile geometry");
+    static_assert(!OWN || (MQ == 5 && NKT == 8 && NKEYS == PKS * 32), "wave-owned products: 4 x 5 + 4 of the band");
+    // frames of a pulled-back tile < NK - HIST - KV_PAD <= NK - KBACK - HIST = the first query that sees key NK - KBACK
+    static_assert(KBACK <= KV_PAD && KBACK % 32 == 0, "a pulled-back tile has no query that sees the rows it replaces");
+    __shared__ __attribute__((aligned(16))) float sp[OWN ? 1 : 4][TQ][NB];  // (per-wave partial) scores, band-relative columns (d, l15)
+    __shared__ __attribute__((aligned(16))) _Float16 ph[16 * MQ][PP];
+    __shared__ __attribute__((aligned(16))) _Float16 pl[16 * MQ][PP];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(tid), g4 = lane >> 4, l15 = lane & 15;
     // XCD-aware placement: the tiles of (batch, head) bh all run on XCD bh % 8
     const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
@@ -65,10 +77,79 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
     const _Float16* qb = q + (long)bh * T * LDQKH;
     const _Float16* kb = kx + ((long)bh * TKP + t0) * LDQKH;
     const _Float16* vb = vx + ((long)bh * TKP + t0) * LDVH;
+    const int kback = t0 + NK - 1 > T + HIST + KV_PAD - 1 ? KBACK : 0;      // scalar: rows the last 32 key rows are pulled back by
 
     AT_STAMP(0);
-    // ---- scores: S[i][n] = <Q[t0+i], Kx[t0+n]>, feature k-steps s = wave, wave+4, ... of 19
-    {
+    // ---- scores: S[i][n] = <Q[t0+i], Kx[t0+n]>
+    if constexpr (OWN) {
+        // Every product sums k-steps ascending, hi*hi, hi*lo, lo*hi.  A wave's six products take Q tile `wave` (its own: straight
+        // from global memory) and Q tile 4 and K tiles wave .. wave+4 (key tile 4 + wave is the last of them), which its
+        // neighbours take too: fetched per wave, 28 fragments a k-step for 13 different ones, the phase ran at the rate of the
+        // bytes it ASKED for (the two workgroups of a CU have four times L1's 32 KB in flight, a line is gone before the next wave
+        // asks: 170e3 cycles of a workgroup's 282e3, profiles/attn_wide_tile_ab.txt).  So the workgroup loads the 8 K tiles and Q
+        // tile 4 of a k-step once, 4.5 16-byte chunks per thread, and shares them through LDS: two staging buffers of 144 rows x
+        // 144 bytes (row stride 36 words: conflict-free ds_read_b128) in the space of `ph` and `sp`, which the phase does not need
+        // before its end; one barrier per k-step, and the global loads run SD steps ahead in registers (7 per step).
+        constexpr int SD = 4, SROW = 72;       // steps in flight; staging row stride in halves
+        static_assert(144 * SROW * 2 <= (int)sizeof(ph) && 144 * SROW * 2 <= (int)sizeof(sp), "staging buffers");
+        _Float16* const stg[2] = {&ph[0][0], reinterpret_cast<_Float16*>(&sp[0][0][0])};
+        f32x4 am[ND + 1];
+#pragma unroll
+        for (int d = 0; d <= ND; ++d) am[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // chunk c = tid + 256 i of a k-step: row c / 8 (0..127: key rows, 128..143: Q tile 4), 16-byte column c % 8
+        const int crow = tid >> 3, ccol = (tid & 7) * 8;
+        const _Float16* const kc = kb + crow * LDQKH + ccol;                                  // + 32 i rows
+        const _Float16* const qc = qb + min(t0 + 64 + (crow & 15), tend - 1) * LDQKH + ccol;  // i = 4: threads 0..127
+        const _Float16* const qw = qb + min(t0 + wave * 16 + l15, tend - 1) * LDQKH + g4 * 16;
+        f16x8 gk[SD][5];
+        Frag gq[SD];
+        auto gload = [&](int s, f16x8 (&dk)[5], Frag& dq) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dk[i] = cp::ld_h8<POL, cp::ATT_K_LD>(kc + (i * 32 - (i == 3 ? kback : 0)) * LDQKH + s * 64);
+            if (wave < 2) dk[4] = cp::ld_h8<POL, cp::ATT_Q_LD>(qc + s * 64);      // wave-uniform
+            dq.h = cp::ld_h8<POL, cp::ATT_Q_LD>(qw + s * 64);
+            dq.l = cp::ld_h8<POL, cp::ATT_Q_LD>(qw + s * 64 + 8);
+        };
+        auto lstore = [&](_Float16* dst, const f16x8 (&sk)[5]) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) *reinterpret_cast<f16x8*>(dst + (crow + 32 * i) * SROW + ccol) = sk[i];
+            if (wave < 2) *reinterpret_cast<f16x8*>(dst + (crow + 128) * SROW + ccol) = sk[4];
+        };
+        auto frag = [&](const _Float16* src, int tile) {
+            const _Float16* p = src + (tile * 16 + l15) * SROW + g4 * 16;
+            return Frag{*reinterpret_cast<const f16x8*>(p), *reinterpret_cast<const f16x8*>(p + 8)};
+        };
+        auto mma3 = [&](f32x4& acc, const Frag& a, const Frag& b) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.h, b.h, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.h, b.l, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.l, b.h, acc, 0, 0, 0);
+        };
+#pragma unroll
+        for (int s = 0; s < SD; ++s) gload(s, gk[s], gq[s]);
+        lstore(stg[0], gk[0]);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < AT_KSTEPS; ++s) {
+            // step s + 1 into the buffer that step s - 1 was read from (the barrier that closed step s - 1 is behind us)
+            if (s + 1 < AT_KSTEPS) lstore(stg[(s + 1) & 1], gk[(s + 1) % SD]);
+            const _Float16* src = stg[s & 1];
+            const Frag q4 = frag(src, 8);
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                const Frag kf = frag(src, wave + d);
+                mma3(am[d], gq[s % SD], kf);
+                if (d == ND - 1) mma3(am[ND], q4, kf);
+            }
+            if (s + SD < AT_KSTEPS) gload(s + SD, gk[s % SD], gq[s % SD]);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) sp[0][wave * 16 + g4 * 4 + r][d * 16 + l15] = am[d][r];
+            if (64 + g4 * 4 + r < TQ) sp[0][64 + g4 * 4 + r][wave * 16 + l15] = am[ND][r];
+        }
+    } else {      // feature k-steps s = wave, wave+4, ... of 19: every wave carries every product, partial sums through `sp`
         f32x4 am[MQ][ND];
 #pragma unroll
         for (int mq = 0; mq < MQ; ++mq)
@@ -131,7 +212,7 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
     // ---- softmax over the 50 slots n = i .. i+49 of query i; 16 threads per query, P as fp16 hi/lo rows
     {
         const float scale = 1.0f / sqrtf((float)DQK);
-        constexpr int NU = AT_PKS * 2;            // 6 column slots of 16 per thread (96 key columns)
+        constexpr int NU = PKS * 2;               // 6 / 8 column slots of 16 per thread (96 / 128 key columns)
 #pragma unroll
         for (int pass = 0; pass < MQ; ++pass) {
             const int ir = pass * 16 + (tid >> 4), sub = tid & 15;
@@ -143,7 +224,10 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                 const int n = sub + 16 * u, j = n - i;
                 const int c = n - pass * 16;           // band-relative column; in [0, 65) whenever j is in the window
                 float s = -3.0e38f;
-                if (j >= 0 && j < WIN) s = (sp[0][i][c] + sp[1][i][c] + sp[2][i][c] + sp[3][i][c]) * scale;
+                if (j >= 0 && j < WIN) {
+                    if constexpr (OWN) s = sp[0][i][c] * scale;
+                    else s = (sp[0][i][c] + sp[1][i][c] + sp[2][i][c] + sp[3][i][c]) * scale;
+                }
                 sv[u] = s;
                 mx = fmaxf(mx, s);
             }
@@ -199,7 +283,9 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                     r = r >= NKEYS ? r - 8 : r;
                     r = r >= NKEYS ? NKEYS - 1 : r;
                 }
-                const _Float16* p = vb + r * LDVH + qc;
+                // OWN: the row is a scalar base and the lane's part one 32-bit offset per column group (as 64-bit lane addresses
+                // the 32 rows of a column group were hoisted out of the loop: 64 registers, and the kernel spilled)
+                const _Float16* p = OWN ? (vb + (32 * ks + j - (ks == 3 ? kback : 0)) * LDVH) + (unsigned)(8 * g4 * LDVH + qc) : vb + r * LDVH + qc;
                 VQuad v;
                 if constexpr (cp::nt(POL, cp::ATT_V_LD)) {        // one 16-byte access, as the plain pair of 8-byte ones is merged into
                     const f16x8 hl = cp::ld_h8<POL, cp::ATT_V_LD>(p);
@@ -213,14 +299,14 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
             }
         };
 #pragma unroll
-        for (int s = 0; s < RING - 1; ++s) fill(s % RING, s % AT_PKS, qcol(wave + 4 * (part + nsplit * (s / AT_PKS))));
+        for (int s = 0; s < RING - 1; ++s) fill(s % RING, s % PKS, qcol(wave + 4 * (part + nsplit * (s / PKS))));
         f32x4 am[MQ][4];
         // fully unrolled (7 column groups for wave 0, 6 for the others): exact vmcnt waits instead of a drain of the
         // ring at every loop back-edge
-        constexpr int NSTEP = ((AT_CG + 3) / 4) * AT_PKS;
+        constexpr int NSTEP = ((AT_CG + 3) / 4) * PKS;
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) {
-            const int ks = s % AT_PKS, cg = wave + 4 * (part + nsplit * (s / AT_PKS));
+            const int ks = s % PKS, cg = wave + 4 * (part + nsplit * (s / PKS));
             if (cg >= AT_CG) break;                    // wave-uniform
             if (ks == 0) {
 #pragma unroll
@@ -229,8 +315,8 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                     for (int c = 0; c < 4; ++c) am[mq][c] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
             {
-                const int sn = s + RING - 1, cgn = wave + 4 * (part + nsplit * (sn / AT_PKS));
-                fill(sn % RING, sn % AT_PKS, qcol(cgn));      // (no `cgn < AT_CG` branch: qcol clamps, the wave's last refill is a re-read)
+                const int sn = s + RING - 1, cgn = wave + 4 * (part + nsplit * (sn / PKS));
+                fill(sn % RING, sn % PKS, qcol(cgn));      // (no `cgn < AT_CG` branch: qcol clamps, the wave's last refill is a re-read)
                 // the refill goes out HERE: without the fence hipcc sinks the loads below this step's MFMAs, next to their
                 // first use (it saves the ring's registers that way) and every step waits out a full V-row load
                 __builtin_amdgcn_sched_barrier(0);
@@ -256,15 +342,19 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                 }
             }
             const int col = cg * 64 + l15 * 4;
-            if (ks == AT_PKS - 1 && col < DV) {
+            if (ks == PKS - 1 && col < DV) {
 #pragma unroll
                 for (int mq = 0; mq < MQ; ++mq)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int t = t0 + mq * 16 + g4 * 4 + r;
+                        float* dst;
+                        // (OWN, 20 rows per lane: the row of (mq, r) and the column group are a scalar base, the lane's part one
+                        // 32-bit offset for the whole kernel)
+                        if constexpr (OWN) dst = (merged + (((long)b * T + t0 + mq * 16 + r) * NH + hd) * DV + cg * 64) + (unsigned)(g4 * 4 * (NH * DV) + l15 * 4);
+                        else dst = &merged[(((long)b * T + t) * NH + hd) * DV + col];
                         if (t < tend && (TQ == 16 * MQ || mq * 16 + g4 * 4 + r < TQ))      // head-major slab [b][t][hd][f][v]: one head's frame is 6208 contiguous bytes
-                            cp::st_f4<POL, cp::ATT_MERGED_ST>(&merged[(((long)b * T + t) * NH + hd) * DV + col],
-                                                              make_float4(am[mq][0][r], am[mq][1][r], am[mq][2][r], am[mq][3][r]));
+                            cp::st_f4<POL, cp::ATT_MERGED_ST>(dst, make_float4(am[mq][0][r], am[mq][1][r], am[mq][2][r], am[mq][3][r]));
                     }
             }
         }
@@ -356,14 +446,36 @@ extern "C" int lh_probe_attn_trace_read(unsigned long long* host_dst) {
 #endif
 namespace lh {
 static int g_attn_mq = 0;              // lh_set_tuning key 4: 0 = automatic, 1 / 2 = query tiles of 16 frames per workgroup,
-                                       // 3 = 40 frames in three tiles
+                                       // 3 = 40 frames in three tiles, 5 = 79 frames in five (the value is the number of MFMA row
+                                       // tiles but for 3's short third tile; four tiles have no kernel and 4 stays refused)
 int attn_set_mq(int v) {
-    if (v < 0 || v > 3) return LH_ERR_ARG;
+    if (v < 0 || v > 5 || v == 4) return LH_ERR_ARG;
     g_attn_mq = v;
     return LH_OK;
 }
 
+// Tile form of a launch, from the WHOLE clip's shape: one 16-frame tile when the clip is that short (streaming: T = 1); two
+// tiles share every K / V row they load (25 instead of 44 KB of L2 traffic per query; 0.36 against 0.43 ms at B = 32); 40
+// frames in three tiles once the launch has more workgroups than the 512 resident ones (12 % fewer K / V rows per query,
+// and at B = 32, T = 625 exactly four rounds of workgroups instead of five: 0.343 against 0.356 ms) — below that a launch
+// is latency-bound and the shorter workgroup wins; 79 frames in five tiles (128 key rows = four whole P.V steps, 1.62 K / V
+// rows per query against 2.23) once even those fill the 512 resident slots twice.
+static int attn_form(int B, int Tshape) {
+    const int bh8 = (B * NH + 7) / 8 * 8;
+    int mq = g_attn_mq;
+    if (Tshape <= 16) mq = 1;
+    else if (mq == 0) mq = (long)bh8 * ((Tshape + 78) / 79) >= 1024 ? 5 : (long)bh8 * ((Tshape + 31) / 32) > 512 ? 3 : 2;
+    return mq;
+}
+static int attn_tq(int mq) { return mq == 5 ? 79 : mq == 3 ? 40 : 16 * mq; }
+
 }  // namespace lh
+
+extern "C" int lh_attn_tile_frames(int B, int T, int* frames) {
+    if (!frames || B <= 0 || T <= 0) return LH_ERR_ARG;
+    *frames = lh::attn_tq(lh::attn_form(B, T));
+    return LH_OK;
+}
 
 extern "C" int lh_local_attn_win(const void* q, const void* kx, const void* vx, float* merged, int B, int T, int t0, int Tc,
                                  lh_stream_t stream) {
@@ -376,16 +488,10 @@ extern "C" int lh_local_attn_win(const void* q, const void* kx, const void* vx, 
     T = Tc;
     const int BH = B * NH;
     const int bh8 = (BH + 7) / 8 * 8;
-    // Query frames per workgroup: one 16-frame tile when the clip is that short (streaming: T = 1); two tiles share
-    // every K / V row they load (25 instead of 44 KB of L2 traffic per query; 0.36 against 0.43 ms at B = 32); 40 frames
-    // in three tiles once the launch has more workgroups than the 512 resident ones (12 % fewer K / V rows per query,
-    // and at B = 32, T = 625 exactly four rounds of workgroups instead of five: 0.343 against 0.356 ms) — below that a
-    // launch is latency-bound and the shorter workgroup wins.  The V ring is two-deep: a three-deep one (228 registers
-    // since the single-accumulator split) measured 3 % slower.
-    int mq = g_attn_mq;
-    if (Tshape <= 16) mq = 1;
-    else if (mq == 0) mq = (long)bh8 * ((Tshape + 31) / 32) > 512 ? 3 : 2;
-    const int tq = mq == 3 ? 40 : 16 * mq;
+    // Query frames per workgroup: attn_form.  The V ring is two-deep: a three-deep one (228 registers since the
+    // single-accumulator split) measured 3 % slower.
+    const int mq = attn_form(B, Tshape);
+    const int tq = attn_tq(mq);
     const int ntt = (T + tq - 1) / tq;
     // latency-bound launches (a handful of workgroups): split the V columns of a tile over 7 workgroups
     const dim3 grid(bh8 * ntt, bh8 * ntt <= 64 ? 7 : 1);
@@ -395,6 +501,10 @@ extern "C" int lh_local_attn_win(const void* q, const void* kx, const void* vx, 
     const bool pol = cp::nt_on((long)B * Tc * NF * C * 4);
     if (mq == 1)
         hipLaunchKernelGGL((k_local_attn<1, 3, 16, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+    else if (mq == 5 && pol)
+        hipLaunchKernelGGL((k_local_attn<5, 2, 79, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+    else if (mq == 5)
+        hipLaunchKernelGGL((k_local_attn<5, 2, 79, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
     else if (mq == 3 && pol)
         hipLaunchKernelGGL((k_local_attn<3, 2, 40, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
     else if (mq == 3)

@@ -804,17 +804,22 @@ class Net(_cabi.HipHost, nn.Module):
         return max(min(K, T // max(self.chunk_min_frames, 1)), 1)
 
     def _window_bounds(self, Bn: int, T: int, K: int) -> list:
-        """Window boundaries [0, ..., T]: even cuts, moved to multiples of the attention kernel's query-tile length (40 frames
-        once the whole-clip launch exceeds 512 workgroups, else 32: lh_attn.hip `lh_local_attn_win`) when the windows are long
-        enough — the windows then cut the time axis into exactly the tiles of the whole-clip launch and the forward is
-        bit-identical to the unchunked one (every other stage is per frame or per sequence)."""
-        bh8 = (Bn * self.n_head + 7) // 8 * 8
-        align = 40 if bh8 * ((T + 31) // 32) > 512 else 32
+        """Window boundaries [0, ..., T]: even cuts, moved to multiples of the attention kernel's query-tile length (the library
+        says which it uses for this batch and clip: `lh_attn_tile_frames`) when the windows are long enough — the windows then
+        cut the time axis into exactly the tiles of the whole-clip launch and the forward is bit-identical to the unchunked one
+        (every other stage is per frame or per sequence)."""
+        frames = ctypes.c_int(0)
+        self._lib(next(self.parameters())).call("lh_attn_tile_frames", Bn, T, ctypes.addressof(frames))
+        align = max(frames.value, 32)                         # (clips of one 16-frame tile are never cut)
         if Bn * self.n_freqs <= self.inter_matvec_max_seqs:
             align = 64                                        # lh_inter_matvec's chunk of steps (a multiple of the 32-frame tile)
         cuts = [(k * T) // K for k in range(K + 1)]
-        if T // K >= 2 * align or (align == 64 and T // K >= 64):
-            cuts = [0] + [int(round(k * T / K / align)) * align for k in range(1, K)] + [T]
+        moved = [0] + [int(round(k * T / K / align)) * align for k in range(1, K)] + [T]
+        # long enough: two tiles per window, or (79-frame tiles at K = 4: 156 frames) every moved window still holds a whole
+        # tile and the frames a window must keep
+        whole = min(b - a for a, b in zip(moved, moved[1:])) >= max(align, self.chunk_min_frames)
+        if T // K >= 2 * align or (align == 64 and T // K >= 64) or whole:
+            cuts = moved
         return cuts
 
     def _lanes(self, dev, K) -> _Lanes:
