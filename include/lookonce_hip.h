@@ -73,7 +73,8 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (28); bumped on any signature change. */
+/* ABI version of this header (29); bumped on any signature or buffer-contract change (29: the LayerNorm eps behind the bias
+ * of lh_qkv_proj_ln*, lh_proj_ln_res*, lh_emb_attn_block and lh_emb_head, below). */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -215,7 +216,11 @@ int lh_linear_res(const float* h, const void* w_pk, const float* bias, const flo
  * K and V rows are written at row (49 + t) of the history-extended buffers.
  *   y      [B][T][97][64]
  *   w_pk   fp16 hi/lo image [7 ntiles][2 ksteps][64 lanes][16] of the stacked weight, rows 0..23 Q(h*6+e),
- *          24..47 K, 48..111 V(h*16+v); bias [112]
+ *          24..47 K, 48..111 V(h*16+v); bias [112 + 3]
+ *          Q, K and V are three LayerNorm groups.  A group whose largest |w| is below 2^-4 is stored as 2^k W, 2^k b (k the
+ *          smallest that brings it to 2^-4 or above; weights.py ln_group), because the un-rescaled lo half of a weight has an
+ *          absolute floor of 2^-25; bias[112..114] = eps 4^k of Q, K, V (1e-5 for k = 0), which the kernel adds to the
+ *          variance: PReLU is positively homogeneous and a power of two exact, so LN_{eps 4^k}(2^k z) = LN_eps(z).
  *   slopes [3] PReLU slopes (Q,K,V);  lnq_w/b, lnk_w/b [608] = the 582 affine values zero-padded;  lnv_w/b [1552]
  *   q, kx, vx  split-precision rows (above)
  *   ring_pos   NULL, or (T = 1 only) a device counter: the K / V row goes to slot (*ring_pos mod 50) of a persistent
@@ -263,7 +268,7 @@ int lh_ring_advance_rows(int* pos, const int* write_pos, int modulo, int n_rows,
 /* A.3.6  attn_concat_proj: Linear(64->64)+PReLU, joint LayerNorm over (f,c), residual; optional speaker gain.
  * Replaces tfgridnet_causal.py:583-588 and, when gain != NULL, the `batch = batch * embed` applied to the
  * input of block 1 (:250-251):  out = (y2 + LN(PReLU(W m + b))) * gain[b][f][c].
- *   merged [B][T][4][97][16] (lh_local_attn's output order); y2, out [B][T][97][64]; w_pk fp16 hi/lo image [4][2][64][16]; bias [64]; slope [1]; ln_w/b [6208]; gain [B][97][64]|NULL
+ *   merged [B][T][4][97][16] (lh_local_attn's output order); y2, out [B][T][97][64]; w_pk fp16 hi/lo image [4][2][64][16]; bias [64 + 1]: b, then eps 4^k of the 2^k W, 2^k b stored (as lh_qkv_proj_ln; all forms of this stage); slope [1]; ln_w/b [6208]; gain [B][97][64]|NULL
  */
 int lh_proj_ln_res(const float* merged, const void* w_pk, const float* bias, const float* slope,
                    const float* ln_w, const float* ln_b, const float* y2, const float* gain, float* out, int B,
@@ -457,9 +462,10 @@ int lh_emb_axis_mv(const float* x, const void* wih_pk, const float* bih, const f
  *   q, k     scratch fp16 [2][4B][T][544] (hi | lo images);  v scratch fp32 [4B][T][1040]
  *   vt       scratch fp16 [2][4B][1040][Tp];  sc scratch fp32 [4B][T][Tp];  p scratch fp16 [2][4B][T][Tp]
  *   wqkv_pk  fp16 hi/lo image [8][2][64][16] of the stacked conv weights [128 x 64] (Q h*8+e | K | V h*16+v)
- *   bqkv, slopes [128] (PReLU slope of each output column's head conv)
+ *   slopes [128] (PReLU slope of each output column's head conv);  bqkv [128 + 12]: the biases, then eps 4^k of the twelve
+ *            LayerNorm groups (Q heads 0..3, K heads 0..3, V heads 0..3), each head conv stored as 2^k W, 2^k b (lh_qkv_proj_ln)
  *   lnq_*, lnk_* [4][520], lnv_* [4][1040]: LayerNorm affine re-ordered to (bin*d + channel)
- *   wproj_pk [4][2][64][16]; bproj [64]; slope_p [1]; lnp_* [4160] re-ordered to (bin*64 + channel)
+ *   wproj_pk [4][2][64][16]; bproj [64 + 1] (b, eps 4^k); slope_p [1]; lnp_* [4160] re-ordered to (bin*64 + channel)
  *   xsplit_next  NULL, or 2*B*T*65*64 fp16: the channel-normalised, split `out` rows for the next block's intra axis call
  *            (lh_emb_axis_fused have_xsplit)
  */
@@ -473,7 +479,7 @@ int lh_emb_attn_block(const float* y2, const void* wqkv_pk, const float* bqkv, c
 /* Enrollment embedder head (reference src/models/tfgridnet_orig/tfgridnet.py:120-127): Linear(65*64 -> 256) per
  * frame, LayerNorm(256), mean over frames.
  *   z [B][T][65][64];  w_pk fp16 hi/lo image [16][130][64][16] of the weight with inputs re-ordered to (bin*64 + c)
- *   bias, ln_w, ln_b [256];  part scratch [B][ceil(T/64)][256];  emb [B][256]
+ *   ln_w, ln_b [256];  bias [256 + 1] (b, then eps 4^k of the 2^k W, 2^k b stored: lh_qkv_proj_ln);  part scratch [B][ceil(T/64)][256];  emb [B][256]
  */
 int lh_emb_head(const float* z, const void* w_pk, const float* bias, const float* ln_w, const float* ln_b,
                 float* part, float* emb, int B, int T, lh_stream_t stream);

@@ -1135,7 +1135,7 @@ __device__ __forceinline__ void efr_zero_pad(_Float16* ahi, _Float16* alo, int t
 // one wave: LayerNorm over ys[f][col0 + c], f < 65, c < D (flat index i = f*D + c), affine gw/gb indexed by i
 template <int D>
 __device__ __forceinline__ void e_ln_head(const float* ys, int yp, int col0, const float* __restrict__ gw,
-                                          const float* __restrict__ gb, float* __restrict__ dst, int lane) {
+                                          const float* __restrict__ gb, float* __restrict__ dst, int lane, float eps) {
     constexpr int N = EF * D, IT = (N + 63) / 64;
     auto at = [&](int k) -> float { const int i = lane + 64 * k; return i < N ? ys[(i / D) * yp + col0 + (i % D)] : 0.f; };
     // the affine of this lane's slots goes into registers FIRST, in flight under the two reductions: read inside the store
@@ -1156,7 +1156,7 @@ __device__ __forceinline__ void e_ln_head(const float* ys, int yp, int col0, con
     float v = 0.f;
 #pragma unroll
     for (int k = 0; k < IT; ++k) { const float dv = at(k) - mean; if (lane + 64 * k < N) v += dv * dv; }
-    const float rstd = rsqrtf(wave_sum(v) * (1.0f / N) + LN_EPS);
+    const float rstd = rsqrtf(wave_sum(v) * (1.0f / N) + eps);
 #pragma unroll
     for (int k = 0; k < IT; ++k) {
         const int i = lane + 64 * k;
@@ -1169,7 +1169,7 @@ constexpr int EQP = 544;                         // 520 features padded to 17 k-
 template <int D>
 __device__ __forceinline__ void e_ln_head_split(const float* ys, int yp, int col0, const float* __restrict__ gw,
                                                 const float* __restrict__ gb, _Float16* __restrict__ dh,
-                                                _Float16* __restrict__ dl, int lane) {
+                                                _Float16* __restrict__ dl, int lane, float eps) {
     constexpr int N = EF * D, IT = (EQP + 63) / 64;
     static_assert(N <= EQP, "row pitch");
     auto at = [&](int k) -> float { const int i = lane + 64 * k; return i < N ? ys[(i / D) * yp + col0 + (i % D)] : 0.f; };
@@ -1187,7 +1187,7 @@ __device__ __forceinline__ void e_ln_head_split(const float* ys, int yp, int col
     float v = 0.f;
 #pragma unroll
     for (int k = 0; k < IT; ++k) { const float dv = at(k) - mean; if (lane + 64 * k < N) v += dv * dv; }
-    const float rstd = rsqrtf(wave_sum(v) * (1.0f / N) + LN_EPS);
+    const float rstd = rsqrtf(wave_sum(v) * (1.0f / N) + eps);
 #pragma unroll
     for (int k = 0; k < IT; ++k) {
         const int i = lane + 64 * k;
@@ -1224,6 +1224,9 @@ __global__ void __launch_bounds__(256, 2) k_emb_qkv(const float* __restrict__ y,
     }
     const int c0 = wave * 16 + l15, c1 = c0 + 64;
     const float bz0 = bias[c0], bz1 = bias[c1], a0 = slopes[c0], a1 = slopes[c1];
+    // LayerNorm eps of this wave's Q, K and V head behind the 128 biases: every head conv is packed as 2^k W, 2^k b with
+    // eps 4^k here (weights.py ln_group; 1e-5 for k = 0) — LN_{eps 4^k}(2^k z) = LN_eps(z)
+    const float eq = bias[ENQKV + wave], ek = bias[ENQKV + NH + wave], ev = bias[ENQKV + 2 * NH + wave];
     efr_zero_pad(ahi, alo, tid);
     const int nframes = B * T;
     float4 stg[EFR_NLD];
@@ -1246,9 +1249,9 @@ __global__ void __launch_bounds__(256, 2) k_emb_qkv(const float* __restrict__ y,
         __syncthreads();
         const int hd = wave, ln = lane + (fr >> 30);          // (fr >> 30) = 0: blocks LICM of the slot addresses
         const long row = ((long)hd * B + b) * T + t;           // head-major batch order [nh*B] like espnet2's torch.cat
-        e_ln_head_split<EE>(ys, YP, hd * EE, lnq_w + hd * EDQK, lnq_b + hd * EDQK, q + row * EQP, q + img + row * EQP, ln);
-        e_ln_head_split<EE>(ys, YP, NH * EE + hd * EE, lnk_w + hd * EDQK, lnk_b + hd * EDQK, k + row * EQP, k + img + row * EQP, ln);
-        e_ln_head<VD>(ys, YP, 2 * NH * EE + hd * VD, lnv_w + hd * EDV, lnv_b + hd * EDV, v + row * EDV, ln);
+        e_ln_head_split<EE>(ys, YP, hd * EE, lnq_w + hd * EDQK, lnq_b + hd * EDQK, q + row * EQP, q + img + row * EQP, ln, eq);
+        e_ln_head_split<EE>(ys, YP, NH * EE + hd * EE, lnk_w + hd * EDQK, lnk_b + hd * EDQK, k + row * EQP, k + img + row * EQP, ln, ek);
+        e_ln_head<VD>(ys, YP, 2 * NH * EE + hd * VD, lnv_w + hd * EDV, lnv_b + hd * EDV, v + row * EDV, ln, ev);
     }
 }
 
@@ -1269,7 +1272,7 @@ __global__ void __launch_bounds__(256, 2) k_emb_proj(const float* __restrict__ m
         const _Float16* p = w_pk + ((long)(wave * 2 + ks) * 64 + lane) * 16;
         wh[ks] = *reinterpret_cast<const f16x8*>(p); wl[ks] = *reinterpret_cast<const f16x8*>(p + 8);
     }
-    const float bz = bias[wave * 16 + l15], a = slope[0];
+    const float bz = bias[wave * 16 + l15], a = slope[0], eps = bias[C];      // eps 4^k behind the 64 biases (weights.py ln_group)
     float4 pw[NSLOT], pb[NSLOT];
 #pragma unroll
     for (int k = 0; k < NSLOT; ++k) {
@@ -1313,7 +1316,7 @@ __global__ void __launch_bounds__(256, 2) k_emb_proj(const float* __restrict__ m
             const float dx = vv[k].x - mean, dy = vv[k].y - mean, dz = vv[k].z - mean, dw = vv[k].w - mean;
             if (tid + 256 * k < N4) vs += dx * dx + dy * dy + dz * dz + dw * dw;
         }
-        const float rstd = rsqrtf(block_sum_256(vs, red) * (1.0f / N) + LN_EPS);
+        const float rstd = rsqrtf(block_sum_256(vs, red) * (1.0f / N) + eps);
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) {
             const int i = tid + 256 * k;
@@ -1866,7 +1869,7 @@ __global__ void __launch_bounds__(512, 1) k_emb_head(const float* __restrict__ z
 #pragma unroll
                 for (int w = 0; w < 8; ++w) v += rs[w][row];
                 if (pass == 0) mean[mt][r] = v * (1.0f / EH_N);
-                else rstd[mt][r] = rsqrtf(v * (1.0f / EH_N) + LN_EPS);
+                else rstd[mt][r] = rsqrtf(v * (1.0f / EH_N) + bias[EH_N]);      // eps 4^k behind the 256 biases (weights.py ln_group)
             }
     }
 #pragma unroll
@@ -2042,8 +2045,8 @@ extern "C" int lh_emb_axis_mv(const float* x, const void* wih_pk, const float* b
 //   y2, out [B][T][65][64]; merged scratch [B][T][65][64]
 //   q, k  scratch fp16 [2][4B][T][544]   (hi | lo images);  v scratch fp32 [4B][T][1040]
 //   vt    scratch fp16 [2][4B][1040][Tp]; sc scratch fp32 [4B][T][Tp]; p scratch fp16 [2][4B][T][Tp]
-//   wqkv_pk fp16 hi/lo image [8][2][64][16] of the stacked 1x1-conv weights [128 x 64]; bqkv, slopes [128];
-//   lnq/lnk [4][520], lnv [4][1040] affine in flat (f*d + c) order; wproj_pk [4][2][64][16]; bproj [64]; slope_p [1];
+//   wqkv_pk fp16 hi/lo image [8][2][64][16] of the stacked 1x1-conv weights [128 x 64]; slopes [128]; bqkv [128 + 12 eps];
+//   lnq/lnk [4][520], lnv [4][1040] affine in flat (f*d + c) order; wproj_pk [4][2][64][16]; bproj [64 + 1 eps]; slope_p [1];
 //   lnp_w/b [4160] in flat (f*64 + c) order
 extern "C" int lh_emb_attn_block(const float* y2, const void* wqkv_pk, const float* bqkv, const float* slopes,
                                  const float* lnq_w, const float* lnq_b, const float* lnk_w, const float* lnk_b,

@@ -276,6 +276,9 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
     const float sq = slopes[0], sk = slopes[1], sv = slopes[2];
     const float a0 = c0 < NH * E ? sq : (c0 < 2 * NH * E ? sk : sv);      // PReLU slope of column c0; c1 is always V
     const bool le1 = sq <= 1.0f && sk <= 1.0f && sv <= 1.0f;            // kernel-uniform: PReLU = max(x, a x)
+    // LayerNorm eps of Q, K, V behind the 112 biases: the packer stores 2^k W, 2^k b per LayerNorm group and eps 4^k here
+    // (weights.py ln_group; 1e-5 for k = 0) — LN_{eps 4^k}(2^k z) = LN_eps(z), at no instruction in the frame loop
+    const float eq = bias[NQKV], ek = bias[NQKV + 1], ev = bias[NQKV + 2];
     // where this lane's columns land in yf: element (f, c) -> base + f * stride
     // (row stride E for Q / K = waves 0..2, VD for V = wave 3: a template argument of qkv_products)
     int base0;
@@ -347,7 +350,7 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
             const float sq1 = lq.read(yq, zero8, ln), sk1 = lk.read(yk, zero8, ln);
             const float mq = wave_sum(sq1) * (1.0f / DQK), mk = wave_sum(sk1) * (1.0f / DQK);
             const float vq = lq.center(mq, ln), vk = lk.center(mk, ln);
-            const float rq = rsqrtf(wave_sum(vq) * (1.0f / DQK) + LN_EPS), rk = rsqrtf(wave_sum(vk) * (1.0f / DQK) + LN_EPS);
+            const float rq = rsqrtf(wave_sum(vq) * (1.0f / DQK) + eq), rk = rsqrtf(wave_sum(vk) * (1.0f / DQK) + ek);
             lq.template store<0, POL>(rq, qrow, ln);
             if (!ROWS || wp >= 0) lk.template store<0, POL>(rk, krow_p, ln);
         }
@@ -358,7 +361,7 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
             const float sv1 = lv.read(yv, zero8, ln);
             const float mv = wave_sum(sv1) * (1.0f / DV);
             const float vv = lv.center(mv, ln);
-            const float rv = rsqrtf(wave_sum(vv) * (1.0f / DV) + LN_EPS);
+            const float rv = rsqrtf(wave_sum(vv) * (1.0f / DV) + ev);
             lv.template store<1, POL>(rv, vrow, ln);
         }
         QKV_STAMP(5);
@@ -417,6 +420,7 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
     load_w<2>(w_pk, wave, lane, wh, wl);   // wave w owns output channels 16w .. 16w+15
     const float bz = bias[wave * 16 + l15];
     const float a = slope[0];
+    const float eps = bias[C];              // eps 4^k of the packed 2^k W, 2^k b (weights.py ln_group), see k_qkv_proj_ln
     // LayerNorm affine of this thread's fixed float4 slots, resident for all frames of the persistent loop
     constexpr int N = NF * C, N4 = N / 4;
     constexpr int NSLOT = (N4 + 255) / 256;      // 7
@@ -499,7 +503,7 @@ __global__ void __launch_bounds__(256, 2) k_proj_ln_res(const float* __restrict_
             d[0] = vs; d[1] = mean; d[2] = v[6].x; d[3] = s;
         }
 #endif
-        const float rstd = rsqrtf(block_sum_256(vs, red) * (1.0f / N) + LN_EPS);
+        const float rstd = rsqrtf(block_sum_256(vs, red) * (1.0f / N) + eps);
         // residual + normalised value per slot, then (block 0 only) ALL speaker-gain loads of the frame, then the stores:
         // vmcnt counts loads and stores in one order, so a gain load issued behind the previous slot's store is usable only
         // once that store has been acknowledged — interleaved, every slot paid a store round trip

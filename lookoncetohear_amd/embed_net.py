@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _cabi
-from .weights import pack_linear_sep as pack_linear_f16x3, pack_mfma_f32, split_f16_unscaled as split_f16      # un-rescaled split (lh_embed.hip ESPLIT = 1)
+from .weights import ln_group, pack_linear_sep as pack_linear_f16x3, pack_mfma_f32, split_f16_unscaled as split_f16      # un-rescaled split (lh_embed.hip ESPLIT = 1)
 
 
 class _LN4D(nn.Module):
@@ -340,9 +340,9 @@ def pack_embedder(sd: Dict[str, torch.Tensor], n_blocks: int) -> dict:
         bp.update(_pack_attn(sd, pre))
         out["blocks"].append(bp)
     # head: Linear input features (c*65 + f) -> (f*64 + c)
-    w = g("embed_proj.0.weight").float()
+    w, b, e = ln_group(g("embed_proj.0.weight"), g("embed_proj.0.bias"))
     out["head_w"] = pack_linear_f16x3(w.reshape(-1, 64, 65).permute(0, 2, 1).reshape(w.shape[0], -1).contiguous())
-    out["head_b"] = g("embed_proj.0.bias").float().contiguous()
+    out["head_b"] = torch.cat([b, e]).contiguous()                                  # [256 | eps 4^k]
     out["head_ln_w"], out["head_ln_b"] = g("embed_proj.1.weight").float().contiguous(), g("embed_proj.1.bias").float().contiguous()
     return out
 
@@ -351,22 +351,25 @@ def _pack_attn(sd, pre, n_head=4):
     """Stacked Q|K|V head convs (columns Q h*8+e, K 32+h*8+e, V 64+h*16+v), per-column PReLU slopes, LayerNorm affines
     re-ordered from [channel][bin] to (bin*d + channel)."""
     g = lambda k: sd[pre + k].float()
-    ws, bs, sl, ln = [], [], [], {}
+    ws, bs, es, sl, ln = [], [], [], [], {}
     for nm in "QKV":
         lw, lb = [], []
         for h in range(n_head):
             q = f"attn_conv_{nm}_{h}."
             w = g(q + "0.weight")
             d = w.shape[0]
-            ws.append(w.reshape(d, 64)); bs.append(g(q + "0.bias")); sl.append(g(q + "1.weight").reshape(1).expand(d))
+            w, b, e = ln_group(w.reshape(d, 64), g(q + "0.bias"))              # every head conv: its own LayerNorm group
+            ws.append(w); bs.append(b); es.append(e); sl.append(g(q + "1.weight").reshape(1).expand(d))
             lw.append(g(q + "2.gamma").reshape(d, -1).t().reshape(-1)); lb.append(g(q + "2.beta").reshape(d, -1).t().reshape(-1))
         ln[nm] = (torch.stack(lw).contiguous(), torch.stack(lb).contiguous())
     q = "attn_concat_proj."
+    wp, bp, ep = ln_group(g(q + "0.weight").reshape(64, 64), g(q + "0.bias"))
     return {
-        "wqkv": pack_linear_f16x3(torch.cat(ws, 0).contiguous()), "bqkv": torch.cat(bs).contiguous(),
+        # bqkv [128 | eps 4^k of Q heads 0..3, K heads 0..3, V heads 0..3], bproj [64 | eps 4^k] (weights.ln_group)
+        "wqkv": pack_linear_f16x3(torch.cat(ws, 0).contiguous()), "bqkv": torch.cat(bs + es).contiguous(),
         "slopes": torch.cat(sl).contiguous(),
         "lnq_w": ln["Q"][0], "lnq_b": ln["Q"][1], "lnk_w": ln["K"][0], "lnk_b": ln["K"][1], "lnv_w": ln["V"][0], "lnv_b": ln["V"][1],
-        "wproj": pack_linear_f16x3(g(q + "0.weight").reshape(64, 64).contiguous()), "bproj": g(q + "0.bias").contiguous(),
+        "wproj": pack_linear_f16x3(wp.contiguous()), "bproj": torch.cat([bp, ep]).contiguous(),
         "slope_p": g(q + "1.weight").reshape(1).contiguous(),
         "lnp_w": g(q + "2.gamma").reshape(64, -1).t().reshape(-1).contiguous(),
         "lnp_b": g(q + "2.beta").reshape(64, -1).t().reshape(-1).contiguous(),

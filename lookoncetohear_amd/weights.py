@@ -8,6 +8,8 @@ one per 16-lane group, so the matching A operand is 32 (or 16) contiguous floats
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 QK_PAD = 608          # Q / K feature rows padded 582 -> 608 (76 blocks of 8; lh_common.h DQKP)
@@ -156,6 +158,26 @@ def pack_linear_sep(w: torch.Tensor) -> torch.Tensor:
     return pack_linear_f16x3(w, unscaled=True)
 
 
+LN_EPS = 1e-5
+
+
+def ln_group(w: torch.Tensor, b: torch.Tensor):
+    """A Linear whose output goes through a PReLU into ONE LayerNorm: -> (2^k w, 2^k b, eps 4^k [1]).
+
+    The un-rescaled split keeps 22 bits of a weight only while |w| >= 2^-3; below that its lo half has an absolute floor of
+    2^-25, so the image's relative precision falls with the layer's scale — which the LayerNorm hides from the float64
+    result.  PReLU is positively homogeneous and a power of two is exact, so LN_{eps 4^k}(2^k z) = LN_eps(z): the packers
+    store 2^k w and 2^k b and the kernels add eps 4^k (which travels behind the bias) instead of the constant.  k is the
+    smallest k >= 0 that brings the group's largest |w| to 2^-4 or above (at most 32): 0 for default-initialised layers,
+    whose images keep their bytes."""
+    m = float(w.detach().abs().max())
+    k = 0
+    if 0.0 < m < 2.0 ** -4 and math.isfinite(m):
+        k = min(-3 - math.frexp(m)[1], 32)                       # m = f 2^e, f in [0.5, 1): 2^k m in [2^-4, 2^-3)
+    eps = torch.full((1,), LN_EPS, dtype=torch.float32, device=w.device) * 4.0 ** k
+    return w.float() * 2.0 ** k, b.float() * 2.0 ** k, eps
+
+
 def pack_block(sd: dict, pre: str) -> dict:
     g = lambda k: sd[pre + k].detach()
     out = {}
@@ -204,16 +226,18 @@ def pack_block(sd: dict, pre: str) -> dict:
     out["inter_b"] = g("inter_rnn.bias_ih_l0") + g("inter_rnn.bias_hh_l0")
     out["inter_lin_w"], out["inter_lin_b"] = pack_linear_sep(g("inter_linear.weight")), g("inter_linear.bias")
     out["inter_lin_wu"] = pack_linear_sep(g("inter_linear.weight"))      # fused kernel (lh_inter_block)
-    out["qkv_w"] = pack_linear_sep(torch.cat([g("attn_conv_Q.0.weight"), g("attn_conv_K.0.weight"),
-                                                g("attn_conv_V.0.weight")], 0))
-    out["qkv_b"] = torch.cat([g("attn_conv_Q.0.bias"), g("attn_conv_K.0.bias"), g("attn_conv_V.0.bias")])
+    # Q, K and V are three LayerNorm groups of one image: each its own power of two (ln_group); bias [112 | eps 4^k of Q, K, V]
+    ws, bs, es = zip(*[ln_group(g(f"attn_conv_{nm}.0.weight"), g(f"attn_conv_{nm}.0.bias")) for nm in "QKV"])
+    out["qkv_w"] = pack_linear_sep(torch.cat(ws, 0))
+    out["qkv_b"] = torch.cat(bs + es)
     out["qkv_slopes"] = torch.cat([g("attn_conv_Q.1.weight"), g("attn_conv_K.1.weight"), g("attn_conv_V.1.weight")])
     for nm in "QKV":
         # Q / K affines zero-padded 582 -> 608: the kernel's pad features then come out as exact zeros
         padn = (QK_PAD - g(f"attn_conv_{nm}.3.norm.weight").numel()) if nm != "V" else 0
         out[f"ln{nm.lower()}_w"] = torch.nn.functional.pad(g(f"attn_conv_{nm}.3.norm.weight"), (0, padn))
         out[f"ln{nm.lower()}_b"] = torch.nn.functional.pad(g(f"attn_conv_{nm}.3.norm.bias"), (0, padn))
-    out["proj_w"], out["proj_b"] = pack_linear_sep(g("attn_concat_proj.0.weight")), g("attn_concat_proj.0.bias")
+    w, b, e = ln_group(g("attn_concat_proj.0.weight"), g("attn_concat_proj.0.bias"))
+    out["proj_w"], out["proj_b"] = pack_linear_sep(w), torch.cat([b, e])      # bias [64 | eps 4^k]
     out["proj_slope"] = g("attn_concat_proj.1.weight")
     out["proj_ln_w"], out["proj_ln_b"] = g("attn_concat_proj.3.norm.weight"), g("attn_concat_proj.3.norm.bias")
     return {k: (v.contiguous() if v.dtype == torch.float16 else v.contiguous().float()) for k, v in out.items()}

@@ -75,6 +75,7 @@ class EmbedRig(Rig):
         self.pk = net._weights(self.dev)
         self.bp = self.pk["blocks"][0]
         self.p = {k: v.detach().double().to(self.dev) for k, v in net.state_dict().items()}
+        self.p32 = {k: v.float() for k, v in self.p.items()}      # the fp32 yardstick's parameters (`yard`: see stage_cases.Rig)
         self.gen = torch.Generator().manual_seed(4321)
 
     # ---- helpers
@@ -193,7 +194,7 @@ class EmbedRig(Rig):
                 return self.bp["lnq_w"] * g, p, (Qh, Kh, Vh, sc, att, O)
         raise AssertionError("no gain factor makes the reference softmax peaked")
 
-    def attn_block(self, B, T, emit_split, peaked=False):
+    def attn_block(self, B, T, emit_split, peaked=False, yard=None):
         self.seed("attn", B, T, emit_split, peaked)
         y2 = self.act(B, T)
         x2 = cf(y2.double())
@@ -231,10 +232,22 @@ class EmbedRig(Rig):
             xs.check("xsplit_next")
             self.finite(xsplit_next=xs.t)
             res["attn.xsplit" + sfx] = rel_err(unsplit(xs.t), E.ln_channels(outr), B)
+        if yard is not None:
+            assert not peaked
+            x32 = cf(y2)
+            Q32, K32, V32 = E.qkv_heads(self.cfg, self.p32, PRE, x32)
+            sc32, att32, O32 = E.attention(self.cfg, Q32, K32, V32)
+            out32 = cl(E.concat_proj_ln_res(self.cfg, self.p32, PRE, O32, x32))
+            yard.update({"attn.q": rel_err(rows(Q32), rows(Qh), nb), "attn.k": rel_err(rows(K32), rows(Kh), nb),
+                         "attn.v": rel_err(rows(V32), rows(Vh), nb), "attn.vt": rel_err(rows(V32), rows(Vh), nb),
+                         "attn.sc": rel_err(sc32, scr, nb), "attn.p": rel_err(att32, att, nb),
+                         "attn.merged": rel_err(cl(O32), cl(Or), B), "attn.out": rel_err(out32, outr, B)})
+            if emit_split:
+                yard["attn.xsplit"] = rel_err(E.ln_channels(out32), E.ln_channels(outr), B)
         return res
 
     # ---- head
-    def head(self, B, T):
+    def head(self, B, T, yard=None):
         self.seed("head", B, T)
         z = self.act(B, T)
         pk = self.pk
@@ -243,7 +256,10 @@ class EmbedRig(Rig):
         self.sync()
         part.check("part"), emb.check("emb")
         self.finite(part=part.t, emb=emb.t)
-        return {"head": rel_err(emb.t, E.head(self.cfg, self.p, cf(z.double())), B)}
+        ref = E.head(self.cfg, self.p, cf(z.double()))
+        if yard is not None:
+            yard["head"] = rel_err(E.head(self.cfg, self.p32, cf(z)), ref, B)
+        return {"head": rel_err(emb.t, ref, B)}
 
 
 # Bounds on max|hip - ref| / max|ref| per utterance, first matching rule wins (a result without a rule is an error).  Set from

@@ -96,6 +96,7 @@ class Rig:
         self.bp = self.pk["blocks"][0]
         sd = {k: v for k, v in net.state_dict().items()}
         self.p = {k: v.to(self.dev) for k, v in O.strip_prefix(sd, torch.float64).items()}
+        self.p32 = {k: v.float() for k, v in self.p.items()}      # the fp32 yardstick's parameters (`yard`, below)
         self.cfg = O.Cfg(**O.TSH_PARAMS)
         self.gen = torch.Generator().manual_seed(1234)
 
@@ -121,6 +122,9 @@ class Rig:
     def g(self, shape, dtype=torch.float32, init=None):
         return Guarded(shape, dtype, self.dev, init)
 
+    # `yard` (a dict, optional argument of some methods): filled with the error of the SAME oracle function evaluated in torch
+    # float32 on the same inputs and parameters, under the names of the returned results — what plain fp32 arithmetic loses
+    # on this case, the yardstick of tests/param_cases.py
     def _ln(self, x, nm):
         return torch.nn.functional.layer_norm(x.double(), (C,), self.p[PRE + nm + ".norm.weight"], self.p[PRE + nm + ".norm.bias"], 1e-5)
 
@@ -128,7 +132,7 @@ class Rig:
         return O._lstm_fast(x, self.p, PRE + nm + ".", h0, c0, bidirectional)
 
     # ---- A.1 front end
-    def stft_conv_in(self, B, T, scales):
+    def stft_conv_in(self, B, T, scales, yard=None):
         ns = 128 * T + 64
         x = self.randn(B, 2, ns, scales=scales)
         cb = self.randn(B, 4, 2, F, scales=[0.5 * s for s in scales])
@@ -137,6 +141,9 @@ class Rig:
         self.sync()
         zr, nb, _ = O.front_end(self.cfg, self.p, x.double(), cb.double())
         z.check("z"), cbo.check("conv_buf_out")
+        if yard is not None:
+            z32, nb32, _ = O.front_end(self.cfg, self.p32, x, cb)
+            yard.update({"stft_conv_in": rel_err(z32, zr, B), "stft_conv_in.conv_buf": rel_err(nb32, nb, B)})
         return {"stft_conv_in": rel_err(z.t, zr, B), "stft_conv_in.conv_buf": rel_err(cbo.t, nb, B)}
 
     # ---- A.2 speaker gain
@@ -292,7 +299,7 @@ class Rig:
         else:
             self.call("lh_qkv_proj_ln_win", *args, *win, self.st)
 
-    def qkv_ring(self, B, T, scales):
+    def qkv_ring(self, B, T, scales, yard=None):
         """K_buf / V_buf -> lh_ring_pack -> lh_qkv_proj_ln -> lh_ring_unpack against Q, K, V and the new history."""
         y = self.randn(B, T, F, C, scales=scales)
         kb, vb = self.randn(B * NH, HIST, QKF), self.randn(B * NH, HIST, VF)
@@ -307,6 +314,9 @@ class Rig:
         assert not bool(kx.t[:, T + HIST:].any()) and not bool(vx.t[:, T + HIST:].any()), "pad rows of kx / vx written"
         Qr, Kr, Vr = O.qkv_proj_ln(self.cfg, self.p, PRE, y.double())
         _, _, kbr, vbr = O.history_concat(self.cfg, kb.double(), vb.double(), Kr, Vr)
+        if yard is not None:
+            Q32, K32, V32 = O.qkv_proj_ln(self.cfg, self.p32, PRE, y)
+            yard.update({"qkv_proj_ln.Q": rel_err(Q32, Qr, B), "qkv_proj_ln.K": rel_err(K32, Kr, B), "qkv_proj_ln.V": rel_err(V32, Vr, B)})
         return {"qkv_proj_ln.Q": rel_err(unsplit_qk(q.t), Qr, B),
                 "qkv_proj_ln.K": rel_err(unsplit_qk(kx.t[:, HIST:HIST + T]), Kr, B),
                 "qkv_proj_ln.V": rel_err(unsplit_v(vx.t[:, HIST:HIST + T]), Vr, B),
@@ -402,7 +412,7 @@ class Rig:
         return worst
 
     # ---- A.3.6 projection + LayerNorm + residual (+ gain)
-    def proj_ln_res(self, B, T, scales, gain=True, win=None):
+    def proj_ln_res(self, B, T, scales, gain=True, win=None, yard=None):
         mg = self.randn(B, T, NH, F, VD)
         y2 = self.randn(B, T, F, C, scales=scales)
         g = self.randn(B, F, C) if gain else None
@@ -424,10 +434,13 @@ class Rig:
         t0, Tc = win if win else (0, T)
         if win:
             out.frames_untouched(o0, 1, t0, Tc, name)
+        if yard is not None:
+            r32 = O.concat_proj_ln_res(self.cfg, self.p32, PRE, Ob.float(), y2)
+            yard[name] = rel_err((r32 * g[:, None] if gain else r32)[:, t0:t0 + Tc], ref[:, t0:t0 + Tc], B)
         return {name: rel_err(out.t[:, t0:t0 + Tc], ref[:, t0:t0 + Tc], B)}
 
     # ---- A.4 back end
-    def deconv_istft(self, B, T, scales, runs=0):
+    def deconv_istft(self, B, T, scales, runs=0, yard=None):
         y = self.randn(B, T, F, C, scales=scales)
         db = self.randn(B, C, 2, F, scales=scales)
         ib = self.randn(B, 2, 2 * F, 1, scales=[0.3 * s for s in scales])
@@ -440,6 +453,10 @@ class Rig:
             t.check(n)
         wr, dr, ir = O.back_end(self.cfg, self.p, y.double(), db.double(), ib.double())
         k = f"deconv_istft.k6={runs}"
+        if yard is not None:
+            w32, d32, i32 = O.back_end(self.cfg, self.p32, y, db, ib)
+            yard.update({k: rel_err(w32[..., :-64], wr[..., :-64], B), k + ".deconv_buf": rel_err(d32, dr, B),
+                         k + ".istft_buf": rel_err(i32, ir, B)})
         return {k: rel_err(wave.t, wr[..., :-64], B), k + ".deconv_buf": rel_err(dbo.t, dr, B),
                 k + ".istft_buf": rel_err(ibo.t, ir, B)}
 
