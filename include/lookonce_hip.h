@@ -697,6 +697,38 @@ enum { LH_ENROLL_ARM = 1, LH_ENROLL_CANCEL = 2, LH_ENROLL_GEN_SHIFT = 8, LH_ENRO
 int lh_session_capture(const float* chunk_in, float* enroll, unsigned* ecmd, unsigned* estate, unsigned* edone, int n_chunks,
                        int S, lh_stream_t stream);
 
+/* Monitor mix (ABI 30): what the listener hears is wet * separated + dry * room.  One more node of the per-chunk graph, after
+ * lh_session_end[_rows][_paced] and ahead of lh_session_resample_out / lh_session_emit_s16, in a host built with a monitor.
+ * It addresses everything by SLOT, in every flavour.  Output row j of a slot covers samples [128 j, 128 j + 128) of the slot's
+ * stream, and those are samples [0, 128) of input row j: the dry path is the input row itself, with no delay line, and the
+ * two paths are aligned to the sample behind whatever framing and resampling the host does around the 16 kHz rows.
+ *   chunk_in   [S][2][192] as above (never written), 16-byte aligned
+ *   out        [S][2][128] the rows lh_session_end* left, 16-byte aligned: a row that does not sound is exact zeros.  Mixed in
+ *              place
+ *   target     [2][S] fp32: the wet targets, then the dry targets, in [0, 1].  Posted by the host like hold (one asynchronous
+ *              copy ahead of the step, only when one changed); read only
+ *   gain       [2][S] fp32: the current wet and dry gains, device-owned; the host sets them to wet 1, dry 0 at start
+ *   hold       [S] the hold words of a paced host, NULL in a lock-step host
+ *   step       1.0f / (float)ramp_samples: a full 0 -> 1 swing takes ramp_samples samples at 16 kHz
+ * Per slot and chunk (one wave per slot, the only writer of the slot's gains and row), for each of the two gains, with g0 its
+ * value at the chunk's start and t its target:
+ *     d = t - g0;   lim = (float)(n + 1) * step  (one fp32 multiply);   g(n) = |d| <= lim ? t : g0 + copysign(lim, d),  n = 0 .. 127
+ * and afterwards gain = g(127): linear, monotone, exactly t at the end, and t may change in mid-ramp.  Then, in this order:
+ *   1. hold[s] != 0: nothing is written — the row is the zeros the end entry point wrote — and both gains stay: the ramp
+ *      resumes with the listener;
+ *   2. wet g0 == t == 1 and dry g0 == t == 0 (the defaults, settled): the row is not touched and keeps the bits, signed zeros
+ *      included, of a host without the node;
+ *   3. dry g0 == t == 0: out = wet(n) * y.  The input row does not enter the result: a NaN there cannot leak through 0 * NaN;
+ *   4. one of the 256 samples chunk_in[s][c][0 .. 127] is inf / NaN: the row is exact zeros, and the gains advance.  No fault
+ *      is reported: an idle slot has none, an open slot's input was judged by lh_session_end.  The look-ahead samples
+ *      128 .. 191 are not part of the row and are not looked at;
+ *   5. otherwise out[s][c][n] = fmaf(wet(n), y, dry(n) * x[s][c][n]), y the row as found.
+ * No atomics, nothing is read back, bit-identical from run to run.
+ * LH_ERR_ARG: a null pointer (hold excepted), chunk_in or out not 16-byte aligned, target / gain / hold not 4-byte aligned,
+ * target == gain, S <= 0, step not in (0, 1] (NaN included).  Neither allocates nor synchronises. */
+int lh_session_mix(const float* chunk_in, float* out, const float* target, float* gain, const unsigned* hold, float step, int S,
+                   lh_stream_t stream);
+
 /* Paced sessions (ABI 19): a listener whose chunk is late is HELD for the step — the other slots are not stalled and the
  * held one is, after the step, bit for bit what it was before.  Every row owns its K / V ring position, so a listener's
  * samples depend on their own chunks only: not on when the slot was opened, not on who else was held.  The entry points

@@ -7,11 +7,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_double, c_int, c_ulonglong, c_void_p
+from ctypes import c_double, c_float, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -39,6 +39,8 @@ SIGNATURES = {
     "lh_session_end": [_P, _I, _P, _P, _P, _P, _P, _I, _P],
     # enrollment capture (ABI 17): the node after lh_session_begin in a SessionStreamer built with enroll_chunks
     "lh_session_capture": [_P] * 5 + [_I, _I, _P],
+    # monitor mix (ABI 30): the node after lh_session_end* in a SessionStreamer built with monitor; hold is NULL in lock-step
+    "lh_session_mix": [_P] * 5 + [c_float, _I, _P],
     # row compaction (ABI 18): the moves and the row forms of the two bracket nodes, SessionStreamer(compact=True)
     "lh_session_move": [_P, _I, _P, _P, _P, _I, _I, _P],
     "lh_session_begin_rows": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],

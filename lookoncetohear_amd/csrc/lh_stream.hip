@@ -539,6 +539,58 @@ __global__ void __launch_bounds__(SC_NT) k_session_capture(const float* __restri
     }
 }
 
+// Monitor mix (ABI 30): one more node of the per-chunk graph, after k_session_end and ahead of the resample / 16-bit node, in a
+// streamer built with a monitor.  Output row j of a slot covers samples [128 j, 128 j + 128) of the slot's stream, and those are
+// the first 128 samples of input row j: the dry path needs no delay line, out = wet y + dry x on the rows as they lie.  Two
+// gains per slot ramp linearly towards the targets the host posts, `step` per sample; the gain of sample n is a function of the
+// gain at the chunk's start, never of sample n - 1, so the lanes share nothing and the ramp lands on its target exactly.
+// k_session_capture's shape: one wave per slot, by SLOT in every form, lane = 32 channel + float4 of the channel, and that wave
+// is the only writer of the slot's gains and (after k_session_end) of its row.  Pure latency again: the four words and the
+// lane's two float4 are requested together before any is looked at; the gains come through lane 0, so every lane holds them
+// before lane 0, the writer below, goes on.
+// PACED: a held slot's row is the zeros k_session_end wrote and its gains wait for the listener.
+static_assert(NSRC * HOP / 4 == SC_NT, "one float4 of the output row per lane, as of the input row");
+__device__ __forceinline__ float mix_gain(float g0, float t, float step, int n) {
+    const float d = t - g0, lim = (float)(n + 1) * step;
+    return fabsf(d) <= lim ? t : g0 + copysignf(lim, d);
+}
+template <bool PACED>
+__global__ void __launch_bounds__(SC_NT) k_session_mix(const float* __restrict__ chunk_in, float* out,
+                                                       const float* __restrict__ target, float* gain,
+                                                       const unsigned* __restrict__ hold, float step, int S) {
+    const int s = blockIdx.x, lane = threadIdx.x, ch = lane >> 5, q = lane & 31;
+    float4* row = reinterpret_cast<float4*>(out + ((long)s * NSRC + ch) * HOP) + q;
+    const float wt = target[s], dt = target[S + s];
+    const float w0 = __shfl(gain[s], 0), d0 = __shfl(gain[S + s], 0);
+    unsigned held = 0u;
+    if constexpr (PACED) held = hold[s];
+    const float4 x = reinterpret_cast<const float4*>(chunk_in + ((long)s * NMIC + ch) * NFFT)[q];
+    const float4 y = *row;
+    if (held != 0u) return;                        // wave-uniform, like everything up to the stores
+    const bool dry_off = d0 == 0.f && dt == 0.f;
+    if (dry_off && w0 == 1.f && wt == 1.f) return;       // settled at the defaults: the row keeps its bits, signed zeros included
+    const int n = 4 * q;
+    float4 r;
+    if (dry_off) {                                 // x is not part of the result: 0 * NaN cannot leak
+        r.x = mix_gain(w0, wt, step, n) * y.x;
+        r.y = mix_gain(w0, wt, step, n + 1) * y.y;
+        r.z = mix_gain(w0, wt, step, n + 2) * y.z;
+        r.w = mix_gain(w0, wt, step, n + 3) * y.w;
+    } else if (wave_any(nonfinite4(x))) {          // no fault: an idle slot has none, k_session_end has judged an open one
+        r = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        r.x = fmaf(mix_gain(w0, wt, step, n), y.x, mix_gain(d0, dt, step, n) * x.x);
+        r.y = fmaf(mix_gain(w0, wt, step, n + 1), y.y, mix_gain(d0, dt, step, n + 1) * x.y);
+        r.z = fmaf(mix_gain(w0, wt, step, n + 2), y.z, mix_gain(d0, dt, step, n + 2) * x.z);
+        r.w = fmaf(mix_gain(w0, wt, step, n + 3), y.w, mix_gain(d0, dt, step, n + 3) * x.w);
+    }
+    *row = r;
+    if (lane == 0) {
+        gain[s] = mix_gain(w0, wt, step, HOP - 1);
+        gain[S + s] = mix_gain(d0, dt, step, HOP - 1);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Suspend / resume (ABI 20): one listener's state out of the buffers as a snapshot, and back into any row of any host of the
 // same model (layout: include/lookonce_hip.h).  Not nodes of the per-chunk graph: the host enqueues them between two chunks,
@@ -1297,5 +1349,22 @@ extern "C" int lh_session_resample_out(const float* out, float* tail, const unsi
     else
         hipLaunchKernelGGL(k_session_resample_out<false>, dim3(S), dim3(RO_NT), 0, (hipStream_t)stream, out, tail, hold, out_client,
                            bank, o, n, width, T);
+    return check_launch();
+}
+
+// ---- monitor mix (ABI 30) -----------------------------------------------------------------------------------------------------
+extern "C" int lh_session_mix(const float* chunk_in, float* out, const float* target, float* gain, const unsigned* hold,
+                              float step, int S, lh_stream_t stream) {
+    using namespace lh;
+    if (!aligned16(chunk_in) || !aligned16(out) || (const void*)chunk_in == (const void*)out || !aligned_to(target, 4) ||
+        !aligned_to(gain, 4) || (const void*)target == (const void*)gain || (hold && !aligned_to(hold, 4)) || S <= 0 ||
+        !(step > 0.f && step <= 1.f))
+        return LH_ERR_ARG;
+    if (hold)
+        hipLaunchKernelGGL((k_session_mix<true>), dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, out, target, gain, hold,
+                           step, S);
+    else
+        hipLaunchKernelGGL((k_session_mix<false>), dim3(S), dim3(SC_NT), 0, (hipStream_t)stream, chunk_in, out, target, gain,
+                           (const unsigned*)nullptr, step, S);
     return check_launch();
 }

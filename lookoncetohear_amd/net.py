@@ -381,7 +381,8 @@ class Net(_cabi.HipHost, nn.Module):
 
     def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
                               compact: bool = False, row_buckets=None, pace: bool = False, packets: bool = False,
-                              fifo_samples: int = 2048, pcm16: bool = False, client_rate: int = 16000):
+                              fifo_samples: int = 2048, pcm16: bool = False, client_rate: int = 16000, monitor: bool = False,
+                              monitor_ramp: int = 256):
         """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
         `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
         enrollment embedder runs beside the chunk loop and the slot opens itself on the result.
@@ -392,9 +393,11 @@ class Net(_cabi.HipHost, nn.Module):
         input — a device FIFO of `fifo_samples` (a power of two >= 256) per slot is re-framed into windows on the device;
         `pcm16`: packets and output are int16.
         `client_rate` (with `packets`): the clients' sample rate, a multiple of 125 Hz; `push` takes and `step` returns PCM at
-        that rate, resampled on the device on the way in and on the way out."""
+        that rate, resampled on the device on the way in and on the way out.
+        `monitor`: every slot has a wet / dry mix (`set_mix`), ramped on the device over `monitor_ramp` 16 kHz samples per
+        full swing; `enroll(slot, embedder, passthrough=True)` lets the listener hear the room while they look."""
         return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets, pace, packets,
-                               fifo_samples, pcm16, client_rate)
+                               fifo_samples, pcm16, client_rate, monitor, monitor_ramp)
 
     def _enroll_side(self, dev) -> _EnrollSide:
         return _EnrollSide(dev, self.enroll_low_priority)
@@ -1481,7 +1484,7 @@ class SessionStreamer:
     second event reports complete hands its rows to the `open` path, and the slot is in `active` and a fresh stream from that
     `step` on.  `enrolling`: the slots capturing or embedding;  `embedding_of(slot)`: the [256] device tensor enrollment
     opened the slot with (keep it to `open` the listener again later).  Meanwhile the slot is idle to the separator: its
-    output rows are exact zeros — a host that wants pass-through audio during the look does that itself.  An inf / NaN among
+    output rows are exact zeros — or their own input, with `passthrough=True` in a monitor streamer (below).  An inf / NaN among
     the recorded samples aborts the capture: the slot is listed by `faults()` and is idle again, to be enrolled or opened at
     once.  `close(slot)` cancels a capture or a running embedding (a result that arrives later is dropped by its
     generation), `reset()` cancels all of them.  Call the embedder once on a clip of this length before the loop starts:
@@ -1567,6 +1570,24 @@ class SessionStreamer:
     The raw ring and the output tail are transport like the FIFO: in no snapshot, untouched by `open`, `close`, `suspend` and
     `resume`; `flush(slot)` and `reset()` clear them, so a flushed slot's stream starts from silence, as torchaudio's left pad
     does.  Enrollment keeps recording the 16 kHz `chunk_in`.
+    Monitor (`monitor=True`; False, the default, builds exactly the object above, launch for launch): what a listener hears is
+    `wet` x their separated rows + `dry` x their own input.  `set_mix(slot, wet, dry)` (finite, in [0, 1]; any slot, idle ones
+    included) holds from the next `step`, `mix_of(slot)` returns the targets.  One more graph node after the end node and ahead of
+    the resample / 16-bit node (`lh_session_mix`, by slot in every flavour) ramps the slot's two gains towards the targets on the
+    device — linear, `monitor_ramp` 16 kHz samples per full swing, exactly on target at the end, re-targetable in mid-ramp — and
+    mixes in place: output row j covers samples [128 j, 128 j + 128) of the slot's stream, the first 128 samples of input row j, so
+    the dry path needs no delay line and is aligned to the sample behind any framing and resampling.  A slot settled at the
+    defaults (1, 0) keeps the bits of a streamer without the node; a held slot's row stays zeros and its ramp waits; a non-finite
+    sample among the row's own 128 silences that row without a fault.  The targets travel like the hold words (a fresh pinned
+    array, one asynchronous copy, only in a step where one changed).  The mix is transport, like the FIFO: in no snapshot,
+    untouched by `open`, `close`, `suspend`, `resume` and row moves; `reset()` puts it back to (1, 0).  `enroll(slot, embedder,
+    passthrough=True)` posts (0, 1) with the arming and (1, 0) in the step that opens the slot: the room, then a click-free
+    cross-fade into the target from the slot's first live chunk.  A slot the device closed for a fault is idle and sounds as an
+    idle slot with its dry gain sounds: fail-open.
+    Re-look (`relook(slot, embedder)`; needs `enroll_chunks`, not `monitor`): the capture runs on an OPEN slot while the separator
+    goes on with the current embedding — the slot is in `active` and in `enrolling`, keeps its row in a compacting streamer, and
+    its output is bit for bit what it would be without the capture — and the finished embedding takes the `set_embedding` path:
+    state kept, `embedding_of(slot)` updated.  `close` cancels the look and closes the session, `suspend` is refused meanwhile.
         ss = net.make_session_streamer(64, "cuda:0", pace=True, packets=True)
         ss.open(0, emb_a); ss.open(1, emb_b)
         while serving:                                       # one tick: whatever arrived, then the chunks that are ready
@@ -1585,7 +1606,7 @@ class SessionStreamer:
 
     def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0, compact: bool = False,
                  row_buckets=None, pace: bool = False, packets: bool = False, fifo_samples: int = 2048, pcm16: bool = False,
-                 client_rate: int = 16000):
+                 client_rate: int = 16000, monitor: bool = False, monitor_ramp: int = 256):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
         if client_rate != self.RATE:
@@ -1611,6 +1632,9 @@ class SessionStreamer:
             if not row_buckets or row_buckets[0] < 1 or row_buckets[-1] != n_slots or \
                     any(a >= b for a, b in zip(row_buckets, row_buckets[1:])):
                 raise ValueError(f"row_buckets must ascend from >= 1 to n_slots = {n_slots}, got {row_buckets}")
+        if isinstance(monitor_ramp, bool) or not isinstance(monitor_ramp, int) or monitor_ramp < 1:
+            raise ValueError(f"monitor_ramp is the number of 16 kHz samples of a full 0 -> 1 swing, an int >= 1, got "
+                             f"{monitor_ramp!r}")
         if enroll_chunks < 0 or enroll_chunks == 1:
             raise ValueError("enroll_chunks must be 0 (no enrollment) or >= 2: the embedder needs 4 STFT frames at stride 64, "
                              "192 samples, and a chunk records 128")
@@ -1719,6 +1743,15 @@ class SessionStreamer:
         self._enroll_faults = set()                         # idle slots whose last capture the device aborted
         self._enrolled = {}                                 # slot -> the embedding enrollment opened it with
         self._epending = {}                                 # slot -> LH_ENROLL_* word for the next step
+        self._relook = set()                                # capturing / embedding slots whose session stays open: `relook`
+        self.monitor, self.monitor_ramp = bool(monitor), monitor_ramp
+        self._passthrough = set()                           # enrolling slots whose mix goes back to (1, 0) with their OPEN
+        if monitor:
+            self._mix = torch.zeros(2, 2, S, device=dev)    # targets [2][S] | gains [2][S]: wet, then dry
+            self._mix[:, 0].fill_(1.0)
+            self._mix_step = float(np.float32(1.0) / np.float32(monitor_ramp))
+            self._targets = [(1.0, 0.0)] * S                # the host's copy of the targets, as fp32 values
+            self._mix_posted = True                         # false: a target changed since the last copy
         if n:
             self._clips = torch.zeros(S, net.num_ch, net.stft_chunk_size * n, device=dev)
             self._ewords = torch.zeros(3, S, dtype=torch.int32, device=dev)      # ecmd | estate: generation, chunks recorded
@@ -1754,6 +1787,14 @@ class SessionStreamer:
             lib.call("lh_ring_advance", P(st.pos), net.local_atten_len, stream)
             lib.call("lh_session_end", ctypes.addressof(self._spans_end[k]), len(self._spans_end[k]), P(self.chunk_in),
                      P(st.out), cmd, active, P(self._fault), S, stream)
+            if self.monitor:
+                self._mix_node(lib, None, stream)
+
+    def _mix_node(self, lib, hold, stream):
+        """The wet / dry mix of a monitor streamer, by slot, on the rows the end node left (`hold`: a paced streamer's)."""
+        P = lambda t: t.data_ptr()
+        lib.call("lh_session_mix", P(self.chunk_in), P(self.out), P(self._mix[0]), P(self._mix[1]), hold, self._mix_step,
+                 self.S, stream)
 
     def _body_rows(self, k: int, n: int):
         """The chunk of a compacting streamer for its leading `n` rows: move -> begin -> (capture) -> chunk -> ring advance ->
@@ -1775,6 +1816,8 @@ class SessionStreamer:
             lib.call("lh_ring_advance", P(st.pos), net.local_atten_len, stream)
             lib.call("lh_session_end_rows", ctypes.addressof(self._spans_end[k]), len(self._spans_end[k]), P(self.chunk_in),
                      P(st.out), P(self.out), cmd, active, P(self._fault), slot_of, row_of, frm, n, S, stream)
+            if self.monitor:
+                self._mix_node(lib, None, stream)
 
     def _body_paced(self, k: int, n: int):
         """The chunk of a paced streamer, lock-step rows (n = 0: every slot is a row) or the leading `n` rows of a compacting
@@ -1810,6 +1853,8 @@ class SessionStreamer:
             else:
                 lib.call("lh_session_end_paced", A(end), len(end), A(carry), len(carry) // 2, P(self.chunk_in), P(st.out), cmd,
                          active, P(self._fault), hold, S, stream)
+            if self.monitor:
+                self._mix_node(lib, hold, stream)
             if self._resampling:                            # the rows at the client's rate, fp32 or 16-bit
                 lib.call("lh_session_resample_out", P(self.out), P(self._tail), hold, P(self.out_client),
                          self.FEED_S16 if self.pcm16 else self.FEED_F32, S, P(self._bank_out), self._o_out, self._n_out,
@@ -1855,6 +1900,35 @@ class SessionStreamer:
         self._enroll_faults.clear()
         self._enrolled.clear()
         self._epending.clear()
+        self._relook.clear()
+        self._passthrough.clear()
+        if self.monitor:                                    # gains and targets: wet 1, dry 0
+            self._mix.zero_()
+            self._mix[:, 0].fill_(1.0)
+            self._targets = [(1.0, 0.0)] * self.S
+            self._mix_posted = True
+
+    def set_mix(self, slot: int, wet: float, dry: float):
+        """From the next `step` on `slot` sounds `wet` x its separated rows + `dry` x its own input samples (a monitor
+        streamer: `monitor=True`), each gain ramped on the device from where it stands, `monitor_ramp` samples per full
+        swing.  Any slot, idle ones included: an idle slot's separated rows are zeros, so it sounds `dry` x the room."""
+        self._slot(slot)
+        if not self.monitor:
+            raise ValueError("this SessionStreamer was built without a monitor: make_session_streamer(..., monitor=True)")
+        wet, dry = float(wet), float(dry)
+        if not (math.isfinite(wet) and math.isfinite(dry) and 0.0 <= wet <= 1.0 and 0.0 <= dry <= 1.0):
+            raise ValueError(f"wet and dry are finite gains in [0, 1], got ({wet}, {dry})")
+        target = (float(np.float32(wet)), float(np.float32(dry)))
+        if target != self._targets[slot]:
+            self._targets[slot] = target
+            self._mix_posted = False
+
+    def mix_of(self, slot: int) -> tuple:
+        """(wet, dry): the targets of `slot`'s mix, as the device gets them (fp32 values)."""
+        self._slot(slot)
+        if not self.monitor:
+            raise ValueError("this SessionStreamer was built without a monitor: make_session_streamer(..., monitor=True)")
+        return self._targets[slot]
 
     def _slot(self, slot: int) -> int:
         if not 0 <= slot < self.S:
@@ -1981,13 +2055,18 @@ class SessionStreamer:
         self._enrolled.pop(slot, None)
         self._open(slot, embed)
 
-    def enroll(self, slot: int, embedder):
+    def enroll(self, slot: int, embedder, passthrough: bool = False):
         """From the next `step` on the rows of idle `slot` are recorded, `enroll_chunks` of them; then
         `embedder(clips [k, 2, 128 enroll_chunks]) -> [k, 256]` (an `EmbedTFGridNet` on this device) runs beside the chunk
-        loop and the slot opens on its row.  Until then the slot's output rows are zeros."""
+        loop and the slot opens on its row.  Until then the slot's output rows are zeros — or, with `passthrough` (a monitor
+        streamer), the listener's own input: the slot's mix goes to (0, 1) with the arming and back to (1, 0) in the step
+        that opens the slot, so the room cross-fades into the target on the slot's first live chunk.  A capture that is
+        aborted or cancelled leaves the mix where it is: the listener keeps the room until `set_mix` says otherwise."""
         self._slot(slot)
         if not self.enroll_chunks:
             raise ValueError("this SessionStreamer was built without enrollment: make_session_streamer(..., enroll_chunks=n)")
+        if passthrough and not self.monitor:
+            raise ValueError("passthrough is the dry path of a monitor streamer: make_session_streamer(..., monitor=True)")
         self.poll()
         if slot in self.active:
             raise ValueError(f"slot {slot} is open: close() it first")
@@ -1999,16 +2078,43 @@ class SessionStreamer:
         self._enrolled.pop(slot, None)
         self._capturing[slot] = (gen, embedder)
         self._epending[slot] = self.ARM | (gen << self.GEN_SHIFT)
+        self._passthrough.discard(slot)
+        if passthrough:
+            self.set_mix(slot, 0.0, 1.0)
+            self._passthrough.add(slot)
+
+    def relook(self, slot: int, embedder):
+        """"Look once" at another speaker without leaving the session: from the next `step` on the rows of OPEN `slot` are
+        recorded as `enroll` records an idle slot's, while the separator goes on with the current embedding — the slot stays
+        in `active` (and is listed by `enrolling` too), keeps its row in a compacting streamer, and its output is bit for bit
+        what it would be without the capture.  The finished embedding takes the `set_embedding` path: the carried state is
+        kept, `embedding_of(slot)` is the new one.  `close` cancels the look and closes the session; an aborted capture leaves
+        the old target in place (the non-finite input faults the session anyway); `suspend` is refused meanwhile."""
+        self._slot(slot)
+        if not self.enroll_chunks:
+            raise ValueError("this SessionStreamer was built without enrollment: make_session_streamer(..., enroll_chunks=n)")
+        self.poll()
+        if slot in self._capturing or slot in self._embedding:
+            raise ValueError(f"slot {slot} is enrolling already")
+        if slot not in self.active:
+            raise ValueError(f"slot {slot} is not open: enroll() it")
+        gen = self._new_gen()
+        self._capturing[slot] = (gen, embedder)
+        self._epending[slot] = self.ARM | (gen << self.GEN_SHIFT)
+        self._relook.add(slot)
 
     def close(self, slot: int):
         """From the next `step` on `slot` is idle: its output rows are exact zeros.  Also acknowledges a fault, and cancels an
-        enrollment in progress: nothing opens later."""
+        enrollment in progress: nothing opens later.  A `relook` is cancelled and its session closed."""
         self._slot(slot)
         if slot in self._capturing or slot in self._embedding:
             if self._capturing.pop(slot, None) is not None:
                 self._epending[slot] = self.CANCEL
             self._embedding.pop(slot, None)                 # the call goes on; its row is dropped by generation
-            return
+            self._passthrough.discard(slot)
+            if slot not in self._relook:
+                return
+            self._relook.discard(slot)                      # ... and the session it ran beside is closed below
         if slot in self._enroll_faults:
             self._enroll_faults.discard(slot)
             return
@@ -2322,7 +2428,11 @@ class SessionStreamer:
                 ready.setdefault(embedder, []).append(s)
             elif w == g | self.ENROLL_FAULT:
                 del self._capturing[s]
-                self._enroll_faults.add(s)
+                self._passthrough.discard(s)                # the mix stays: the listener keeps the room
+                if s in self._relook:                       # the session has its own fault word; the old target stays
+                    self._relook.discard(s)
+                else:
+                    self._enroll_faults.add(s)
         for embedder, slots in ready.items():               # one call per embedder: a batch in ascending slot order
             gens = [self._capturing.pop(s)[0] for s in slots]
             # views and a copy on the side stream: nothing here moves host memory, so nothing waits
@@ -2337,8 +2447,17 @@ class SessionStreamer:
             for i, s in enumerate(slots):
                 if self._embedding.get(s) == gens[i]:       # else: cancelled (and perhaps enrolling again) meanwhile
                     del self._embedding[s]
+                    if s in self._relook:                   # the session goes on: `set_embedding`, state kept
+                        self._relook.discard(s)
+                        if s in self.active:                # else the device closed it meanwhile: nothing to re-target
+                            self._enrolled[s] = out[i]
+                            self.set_embedding(s, out[i])
+                        continue
                     self._enrolled[s] = out[i]
                     self._open(s, out[i])
+                    if s in self._passthrough:              # with the OPEN: the cross-fade starts on the first live chunk
+                        self._passthrough.discard(s)
+                        self.set_mix(s, 1.0, 0.0)
 
     def step(self, chunks: Optional[torch.Tensor] = None, present=None) -> torch.Tensor:
         """chunks [S, 2, 192] (rows of idle slots are ignored) -> [S, 2, 128] (rows of idle slots are zeros); a view the next
@@ -2399,6 +2518,11 @@ class SessionStreamer:
                 words[slot] = w
             self._epending.clear()
             self._ewords[0].copy_(src, non_blocking=True)
+        if self.monitor and not self._mix_posted:           # the mix targets too: bit patterns of fp32, [2][S]
+            src = self.net._host_words(2 * self.S, self.device)
+            src.numpy().view(np.float32).reshape(2, self.S)[:] = np.asarray(self._targets, dtype=np.float32).T
+            self._mix[0].view(torch.int32).copy_(src.view(2, self.S), non_blocking=True)
+            self._mix_posted = True
         if self._resumes:
             self._restore()
         if not self.packets:

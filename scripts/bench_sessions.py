@@ -46,6 +46,12 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         present, a chunk's worth of client samples per slot and step (384 at 48 kHz) against the 16 kHz packet streamer fed 128,
         blocks of the two interleaved in one run; `scatter` is the spread of the 16 kHz blocks' p50.  Then the offline
         `Resampler(client_rate, 16000)` on [64, 240000]: bytes read and written over the p50 time against the 8 TB/s of HBM.
+    python scripts/bench_sessions.py --monitor [--batches 1,64] [--out profiles/monitor_cost.txt]
+        what the monitor mix node costs, in DEVICE time per chunk as above, every slot open, the same streamer built with
+        `monitor=False` and with `monitor=True`, blocks of the two interleaved in one run, in three states of the node: (a) settled
+        at the defaults (the node returns after its loads), (b) both gains of every slot ramping through the whole block, (c)
+        every slot settled at a mix of dry and wet.  `scatter` is the spread of the `monitor=False` blocks' p50; the bar for a
+        difference is three times that.
 """
 import argparse
 import json
@@ -553,6 +559,61 @@ def client_rate_bench(net, args):
             f.write(text + "\n")
 
 
+def monitor_bench(net, args):
+    reps = 4
+    lines = [f"monitor mix cost, device time per chunk (HIP events around each replay), every slot open, {args.steps} steps per "
+             f"figure in {reps} interleaved blocks after {args.warmup} warm-up; the yardstick is the SessionStreamer built with "
+             f"monitor=False in the same run; the bar for a difference is three times the scatter of its blocks' p50"]
+    never = 128 * 4 * (args.steps + args.warmup)           # a ramp that outlasts every step of state (b)
+    for B in [int(b) for b in args.batches.split(",")]:
+        d = synth.batch(list(range(B)), 80000)
+        mix = torch.nn.functional.pad(d["mixture"], (0, 64)).to(DEV)
+        emb = d["embedding_gt"][:, 0].to(DEV)
+        chunks = [mix[:, :, i * 128:i * 128 + 192].contiguous() for i in range(625)]
+        mk = net.make_session_streamer
+        off = mk(B, DEV)
+        states = [("(a) settled at the defaults", mk(B, DEV, monitor=True), None),
+                  ("(b) every slot ramping", mk(B, DEV, monitor=True, monitor_ramp=never), (0.0, 1.0)),
+                  ("(c) every slot dry + wet", mk(B, DEV, monitor=True, monitor_ramp=1), (0.7, 0.3))]
+        for ss in [off] + [st[1] for st in states]:
+            for s in range(B):
+                ss.open(s, emb[s])
+        dev_steps(off, chunks, 0, args.warmup)
+        for name, on, target in states:
+            if target is not None:
+                for s in range(B):
+                    on.set_mix(s, *target)
+            dev_steps(on, chunks, 0, args.warmup)
+            ms, p50s = {"off": [], "on": []}, []
+            for rep in range(reps):
+                blk = [a.elapsed_time(b) for a, b in dev_steps(off, chunks, 0, args.steps // reps)]
+                ms["off"] += blk
+                p50s.append(pct(blk, 0.5))
+                ms["on"] += [a.elapsed_time(b) for a, b in dev_steps(on, chunks, 0, args.steps // reps)]
+            torch.cuda.synchronize()
+            assert off.faults() == [] and on.faults() == [] and len(on.active) == B
+            gains = on._mix[1].cpu()
+            if target is None:
+                assert gains.tolist() == [[1.0] * B, [0.0] * B]
+            elif on.monitor_ramp == never:
+                assert (gains[0] > 0).all() and (gains[1] < 1).all(), "the ramp ended inside the measurement"
+            ro, rn = stats(ms["off"]), stats(ms["on"])
+            cost, scatter = rn["p50_ms"] - ro["p50_ms"], max(p50s) - min(p50s)
+            lines.append(f"{name:30s} S={B:3d}   monitor=False: p50 {ro['p50_ms']:.4f} p99 {ro['p99_ms']:.4f} ms   monitor=True: p50 "
+                         f"{rn['p50_ms']:.4f} p99 {rn['p99_ms']:.4f} ms   difference {1e3 * cost:+.1f} us "
+                         f"({100.0 * cost / ro['p50_ms']:+.1f} %), scatter of the monitor=False blocks {1e3 * scatter:.1f} us: "
+                         f"{'WITHIN' if abs(cost) <= 3 * scatter else 'NOT within'} three times the scatter")
+        del off, states
+    lines.append("for scale, the per-node figures README.md gives (rocprofv3 averages, B = 1 / 64): k_session_begin 2.4 / 6.3 us, "
+                 "k_session_end 6.0 / 7.5 us; k_session_capture, the node of this one's shape (one wave per slot, one float4 per "
+                 "lane), has no figure there yet")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def suspend_many_bench(net, args):
     from lookoncetohear_amd import _cabi
 
@@ -644,6 +705,7 @@ def main():
     ap.add_argument("--suspend-many", action="store_true")
     ap.add_argument("--packets", action="store_true")
     ap.add_argument("--client-rate", type=int, default=0)
+    ap.add_argument("--monitor", action="store_true")
     ap.add_argument("--many", default="1,8,64")
     ap.add_argument("--tiles", default="")
     ap.add_argument("--slots", type=int, default=64)
@@ -674,6 +736,8 @@ def main():
         return packets_bench(net, args)
     if args.client_rate:
         return client_rate_bench(net, args)
+    if args.monitor:
+        return monitor_bench(net, args)
     rows = []
     for B in [int(b) for b in args.batches.split(",")]:
         d = synth.batch(list(range(B)), 80000)
