@@ -1,4 +1,4 @@
-"""CPU: `SessionStreamer(compact=True)` (net.py) and its three kernels (`lh_session_move`, `lh_session_begin_rows`,
+"""CPU: `SessionStreamer(compact=True)` (sessions.py) and its three kernels (`lh_session_move`, `lh_session_begin_rows`,
 `lh_session_end_rows`, lh_stream.hip) over the emulated library, eager.  Open listeners live in the leading rows; a listener
 that leaves makes the survivors above move down, and a chunk is launched for the bucket of the rows in use.  A move is a copy
 of bytes, so the claims about it are `torch.equal` on integers; a session is compared with the oracle's forward over its OWN

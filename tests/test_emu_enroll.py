@@ -1,5 +1,5 @@
 """CPU: enrollment from a listener's own stream — `lh_session_capture` (lh_stream.hip) by direct C-ABI calls, and
-`SessionStreamer.enroll / poll` (net.py) over the emulated library, eager.  The side stream of the GPU host is replaced by a
+`SessionStreamer.enroll / poll` (sessions.py) over the emulated library, eager.  The side stream of the GPU host is replaced by a
 synchronous stand-in here (as `SerialLanes` replaces `_Lanes`): every other host line is the one the GPU runs.  Copies and
 isolation claims are `torch.equal`; a session's reference is the oracle's fresh stream within the emulator tolerance of
 tests/test_emu_kernels.py.  Small on purpose: the emulator runs a chunk row in ~0.5 s."""

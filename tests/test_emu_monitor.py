@@ -1,5 +1,5 @@
 """CPU: the monitor mix (ABI 30) — `lh_session_mix` (lh_stream.hip) by direct C-ABI calls on hand-made buffers, and
-`SessionStreamer(monitor=True)`: `set_mix`, `enroll(..., passthrough=True)` and `relook` (net.py) over the emulated library,
+`SessionStreamer(monitor=True)`: `set_mix`, `enroll(..., passthrough=True)` and `relook` (sessions.py) over the emulated library,
 eager.  No claim here is about the separator's arithmetic: the mix is held to the numpy-fp32 restatement of
 tests/monitor_cases.py and everything else to a twin streamer, all bit for bit.  Small on purpose: the emulator runs a chunk
 row in ~0.5 s, so the host cases share one reference run and stay at S = 2 and a handful of chunks."""

@@ -1,4 +1,4 @@
-"""CPU: `SessionStreamer(pace=True)` (net.py) and its entry points (`lh_qkv_proj_ln_rows`, `lh_ring_advance_rows`,
+"""CPU: `SessionStreamer(pace=True)` (sessions.py) and its entry points (`lh_qkv_proj_ln_rows`, `lh_ring_advance_rows`,
 `lh_session_{begin,end,move,capture}_paced` and the row forms; lh_pointwise.hip, lh_attn.hip, lh_stream.hip) over the emulated
 library, eager.  A listener whose chunk is late is HELD for the step: nothing of theirs is judged, their output row is zeros
 and every bit of their state is afterwards what it was before — a hold copies bytes, so those claims are `torch.equal` on

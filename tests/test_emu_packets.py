@@ -1,5 +1,5 @@
 """CPU: packets (ABI 22) — `lh_session_feed`, `lh_session_frame`, `lh_session_emit_s16` (lh_stream.hip) and
-`SessionStreamer(pace=True, packets=True)` (net.py) over the emulated library, eager.  The feature moves bytes and derives
+`SessionStreamer(pace=True, packets=True)` (sessions.py) over the emulated library, eager.  The feature moves bytes and derives
 presence from two counters, so every claim is `torch.equal`: FIFO contents as 32-bit patterns (NaN and inf among them), the
 counters across the ring's end and across 2^32, and a listener's output rows against `step(windows, present)` of a second paced
 streamer.  Small on purpose: the emulator runs a chunk row in ~0.5 s."""

@@ -1,5 +1,5 @@
 """CPU: client-rate resampling (ABI 23) — `lh_resample` (lh_render.hip), `lh_session_resample_in`, `lh_session_resample_out`
-(lh_stream.hip) and `SessionStreamer(pace=True, packets=True, client_rate=...)` (net.py) over the emulated library, eager.
+(lh_stream.hip) and `SessionStreamer(pace=True, packets=True, client_rate=...)` (sessions.py) over the emulated library, eager.
 `lh_resample` is held to the float64 restatement of tests/resample_cases.py within the derived fp32 dot-product bound; the
 session nodes share its inner product, so everything they make is `torch.equal` to `lh_resample` of the whole stream."""
 import ctypes

@@ -1,4 +1,4 @@
-"""CPU: `SessionStreamer` (net.py) and its two kernels (`lh_session_begin` / `lh_session_end`, lh_stream.hip) over the emulated
+"""CPU: `SessionStreamer` (sessions.py) and its two kernels (`lh_session_begin` / `lh_session_end`, lh_stream.hip) over the emulated
 library, eager.  Listener slots open, close, are re-used and fail one at a time while the batch goes on in lock-step.
 The reference of a session is the oracle's forward over the session's OWN samples from the zero state (streaming == offline,
 `O.predict(..., None, pad=False)`), within the emulator tolerance of tests/test_emu_kernels.py; isolation and equality

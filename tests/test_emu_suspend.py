@@ -1,4 +1,4 @@
-"""CPU: `SessionStreamer.suspend` / `resume`, `SessionSnapshot` (net.py) and their entry points `lh_session_save` /
+"""CPU: `SessionStreamer.suspend` / `resume`, `SessionSnapshot` (sessions.py) and their entry points `lh_session_save` /
 `lh_session_restore` (lh_stream.hip) over the emulated library, eager.  A snapshot is bytes: what a listener owns is copied out
 of one set of buffers and into another, so every claim about state is `torch.equal` on integers, NaN and inf patterns among
 them; a resumed listener's output is `torch.equal` to the uninterrupted run.  Small on purpose: the emulator runs a chunk row

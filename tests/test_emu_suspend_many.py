@@ -1,4 +1,4 @@
-"""CPU: `SessionStreamer.suspend_many` / `resume_many` / `drain`, `SessionSnapshotBatch` (net.py) and their entry points
+"""CPU: `SessionStreamer.suspend_many` / `resume_many` / `drain`, `SessionSnapshotBatch` (sessions.py) and their entry points
 `lh_session_save_rows` / `lh_session_restore_rows` / `lh_embed_proj_ln_rows` over the emulated library, eager.  The batched forms
 claim to be the single forms, many at once: every check here is `torch.equal` against `lh_session_save` / `lh_session_restore` /
 `suspend` / `resume` on a twin — bytes, NaN and inf patterns among them.  The hand-made buffers are those of
