@@ -946,6 +946,37 @@ int lh_session_resample_in(const float* raw, int R_in, const lh_resample_item_t*
 int lh_session_resample_out(const float* out, float* tail, const unsigned* hold, void* out_client, int format, int S,
                             const float* bank, int o, int n, int width, lh_stream_t stream);
 
+/* Any rate (ABI 31): the out node for client rates that are no multiple of 125 Hz — 44 100 Hz (o = 160, n = 441), 22 050, 11 025,
+ * 88 200 — where a 128-sample chunk is not a whole number of client samples (352.8 at 44.1 kHz).  The hop is FRACTIONAL: a live
+ * step of a slot yields floor(128 n / o) or ceil(128 n / o) samples, counted on the device and mirrored by the host in the same
+ * integers, so nothing is read back.  With (width, o, n) of the 16 kHz -> client bank and K = 2 width + o:
+ *     d = width + o - 1          the delay at 16 kHz: the least at which every tap of a step's outputs lies in rows already made
+ *     P = o / gcd(128, o)        live steps per period (5 for 44.1 / 22.05 / 11.025 kHz, 1 where o divides 128)
+ *     r in [0, P)                the slot's phase: live steps taken, mod P;   c(r) = floor(128 r n / o)
+ *     T = K + o + ceil(o / n) - 1        carried samples (334 toward 44.1 kHz, 1299 toward 11.025 kHz)
+ * A live step at phase r emits samples m in [c(r), c(r + 1)) of the current period; with m = q n + p and xs = the slot's tail
+ * followed by the chunk's 128-sample row,
+ *     sample m = sum_{k < K} xs[q o - width - d - 128 r + T + k] * bank[p][k]
+ * in the arithmetic above (one fp32 accumulator from +0, one fmaf per tap, ascending k, no tap skipped).  Then the tail is the
+ * last T samples of xs and the phase (r + 1) mod P.  The zeroed tail at start is the left pad and the delay in one: the
+ * concatenation of a slot's live steps equals lh_resample of d zeros followed by its live rows, bit for bit.  Toward 44.1 kHz the
+ * counts of a period are 352, 353, 353, 353, 353.
+ *   out        [S][2][128]  the 16 kHz rows                      tail   [S][2][T], zero at start
+ *   phase      [S] unsigned, zero at start: the kernel is its only writer besides the host's zeroing (flush, reset).  A word
+ *              outside [0, P) is reduced mod P before any index is formed: no value of it moves an address out of the staged span
+ *   hold       [S]; hold[s] != 0: a zero row, count 0, tail and phase untouched
+ *   out_client [S][2][hop_max], hop_max = ceil(128 n / o), float (LH_FEED_F32) or int16 (LH_FEED_S16, the rounding of
+ *              lh_session_emit_s16); samples at and beyond the slot's count are zeros.  Rows of 353 samples cannot be aligned:
+ *              only the base pointers of out, tail and out_client need 16 bytes
+ *   count      [S] int: the valid samples of each slot's row in this step
+ *   bank_t     [K][n] fp32: the TRANSPOSED image of the bank (the same values), so that the 64 consecutive phases of a wave read
+ *              64 consecutive floats per tap
+ * One workgroup per slot, [tail | row] staged in LDS: 1427 floats per channel, what 11 025 Hz needs.
+ * LH_ERR_ARG: a null or misaligned pointer, two arguments naming one buffer, o or n outside [1, 4096], width < 1, T + 128 > 1427,
+ * an unknown format, S <= 0.  Does not allocate, synchronise or read device memory on the host. */
+int lh_session_resample_out_any(const float* out, float* tail, unsigned* phase, const unsigned* hold, void* out_client, int* count,
+                                int format, int S, const float* bank_t, int o, int n, int width, lh_stream_t stream);
+
 /* The path's ONE exchange step, for hosts that drive this ABI without Python: all-reduce (sum) of the
  * fp64 metric sums written by lh_metric_sums over one process per GPU — RCCL over xGMI, 32 bytes, latency-bound.
  * Replaces the reference's Lightning `sync_dist` all-reduce (src/ts_hear_embed_pl_module.py:82-107).  RCCL is bound

@@ -11,7 +11,7 @@ from ctypes import c_double, c_float, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -71,6 +71,8 @@ SIGNATURES = {
     "lh_resample": [_P, _P, _P] + [_I] * 6 + [_P],
     "lh_session_resample_in": [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P],
     "lh_session_resample_out": [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P],
+    # any rate (ABI 31): the out node with a fractional hop, 44.1 kHz clients; SessionStreamer(..., client_rate=44100, any_rate=True)
+    "lh_session_resample_out_any": [_P] * 6 + [_I, _I, _P, _I, _I, _I, _P],
     "lh_proj_ln_res": [_P] * 9 + [_I, _I, _P],
     "lh_deconv_istft": [_P] * 10 + [_I, _I, _I, _P],
     # time windows (ABI 14): the five block stages on frames [t0, t0 + Tc) of [B][T][97][64] buffers (net.py `time_chunks`)

@@ -1,5 +1,5 @@
 // Polyphase sinc resampling (include/lookonce_hip.h, ABI 23): the ONE inner product of lh_resample (lh_render.hip) and of the
-// two session nodes lh_session_resample_in / lh_session_resample_out (lh_stream.hip).
+// session nodes lh_session_resample_in / lh_session_resample_out / lh_session_resample_out_any (lh_stream.hip).
 //
 // With g = gcd(orig, new), o = orig / g, n = new / g, K = 2 width + o, output block q and phase p:
 //     y[q n + p] = sum_{k < K} xpad[q o + k] * bank[p][k]          xpad = width zeros, x, zeros
@@ -31,6 +31,22 @@ __device__ __forceinline__ float resample_dot(const Tap tap, const float* __rest
     float acc = 0.f;
     for (int k = 0; k < K; ++k) acc = fmaf(tap(k), row[k], acc);
     return acc;
+}
+
+// The same chain twice, for the two channels of one output, against a column of the transposed image bankT[K][n] (`col` =
+// bankT + p): tap k of phase p lies at col[k n], so the 64 consecutive phases of a wave read 64 consecutive floats.
+template <class Tap>
+__device__ __forceinline__ void resample_dot2_t(const Tap tap0, const Tap tap1, const float* __restrict__ col, int n, int K,
+                                                float& y0, float& y1) {
+    float a0 = 0.f, a1 = 0.f;
+#pragma unroll 16                              // 16 bank loads in flight per wave: the loop is bound by their latency, not by the fmaf
+    for (int k = 0; k < K; ++k) {
+        const float b = col[(long)k * n];
+        a0 = fmaf(tap0(k), b, a0);
+        a1 = fmaf(tap1(k), b, a1);
+    }
+    y0 = a0;
+    y1 = a1;
 }
 
 // what every entry point accepts: the tile of k_resample must hold one block's taps

@@ -961,6 +961,74 @@ __global__ void __launch_bounds__(RO_NT) k_session_resample_out(const float* __r
     }
 }
 
+// Any rate (ABI 31): the out node where o does not divide 128 (44.1 kHz: o = 160, n = 441) — a FRACTIONAL hop.  A period of
+// P = o / gcd(128, o) live steps consumes 128 P samples, a whole number of blocks, and makes 128 P n / o outputs; the step at
+// phase r of its slot emits outputs [c(r), c(r + 1)) of the period, c(r) = floor(128 r n / o): floor or ceil of 128 n / o of
+// them, counted here and mirrored by the host in the same integers.  Output m = q n + p reads the K taps that start at 16 kHz
+// sample q o - width - d of the period, d = width + o - 1 the fixed delay: in [tail | row], T = K + o + ceil(o / n) - 1 carried
+// samples and the 128 new ones (the row starts at sample 128 r of the period), that is index q o - 128 r + T - width - d.  For
+// r < P and m in [c(r), c(r + 1)):  128 r - (o - 1) <= q o <= 128 r + 127, so the K taps lie in [T - K - o + 2, T + 128).
+// One workgroup per slot; a thread makes BOTH channels of its outputs from one read of the bank, which is the transposed
+// image [K][n]: the 64 outputs of a wave have consecutive phases p (wrapping at n once at most), so a tap is 64 consecutive
+// floats, and the outputs of one block q share their LDS address (a broadcast).  The slot's phase word, count word and tail
+// have this workgroup as their one writer.
+// 512 threads: the 353 outputs of a 44.1 kHz step are one round, and a thread's chain of K dependent fmaf is the kernel's length
+constexpr int RA_NT = 512, RA_XS = 1427;       // staged samples per channel: what 11 025 Hz needs, T = 1299 and the chunk
+template <bool S16>
+__global__ void __launch_bounds__(RA_NT) k_session_resample_out_any(const float* __restrict__ out, float* __restrict__ tail,
+                                                                    unsigned* __restrict__ phase, const unsigned* __restrict__ hold,
+                                                                    void* __restrict__ out_client, int* __restrict__ count,
+                                                                    const float* __restrict__ bank_t, int o, int n, int width,
+                                                                    int T, int P, int Q, int hop_max) {
+    static_assert(NSRC == 2, "resample_dot2_t makes the two channels of an output");
+    __shared__ float xs[NSRC][RA_XS];
+    const int s = blockIdx.x, tid = threadIdx.x, K = 2 * width + o, len = T + HOP;
+    float* row32 = reinterpret_cast<float*>(out_client) + (long)s * NSRC * hop_max;
+    short* row16 = reinterpret_cast<short*>(out_client) + (long)s * NSRC * hop_max;
+    if (hold[s] != 0u) {                                       // block-uniform: a zero row, count 0, tail and phase stay
+        for (int e = tid; e < NSRC * hop_max; e += RA_NT) {
+            if constexpr (S16) row16[e] = 0;
+            else row32[e] = 0.f;
+        }
+        if (tid == 0) count[s] = 0;
+        return;
+    }
+    const int r = (int)(phase[s] % (unsigned)P);               // whatever the word holds: r < P before any index is formed
+    // c(r) = 128 r n / o = Q r n / P with Q = 128 / gcd(128, o): Q (r + 1) n <= 128 * 4096 * 4096 = 2^31, unsigned 32-bit
+    const unsigned Qn = (unsigned)Q * (unsigned)n;
+    const int c0 = (int)(Qn * (unsigned)r / (unsigned)P), cnt = (int)(Qn * (unsigned)(r + 1) / (unsigned)P) - c0;
+    float* tl = tail + (long)s * NSRC * T;
+    const float* row = out + (long)s * NSRC * HOP;
+    for (int i = tid; i < NSRC * len; i += RA_NT) {
+        const int ch = i / len, j = i - ch * len;
+        xs[ch][j] = j < T ? tl[ch * T + j] : row[ch * HOP + j - T];
+    }
+    __syncthreads();                                           // the old tail and the phase word have been read by everyone
+    const int base0 = T - 2 * width - o + 1 - HOP * r;
+    for (int j = tid; j < hop_max; j += RA_NT) {
+        float v0 = 0.f, v1 = 0.f;                              // at and beyond the count: zeros
+        if (j < cnt) {
+            const int m = c0 + j, q = m / n, p = m - q * n, base = base0 + q * o;
+            resample_dot2_t(TapSpan{xs[0] + base}, TapSpan{xs[1] + base}, bank_t + p, n, K, v0, v1);
+        }
+        if constexpr (S16) {
+            row16[j] = (short)emit_s16(v0);
+            row16[hop_max + j] = (short)emit_s16(v1);
+        } else {
+            row32[j] = v0;
+            row32[hop_max + j] = v1;
+        }
+    }
+    for (int i = tid; i < NSRC * T; i += RA_NT) {
+        const int ch = i / T, j = i - ch * T;
+        tl[i] = xs[ch][HOP + j];
+    }
+    if (tid == 0) {
+        phase[s] = r + 1 == P ? 0u : (unsigned)(r + 1);
+        count[s] = cnt;
+    }
+}
+
 }  // namespace lh
 
 extern "C" int lh_intra_stream(const float* x, const void* wih_pk, const float* b_sum, const float* whh, float* h_out,
@@ -1349,6 +1417,33 @@ extern "C" int lh_session_resample_out(const float* out, float* tail, const unsi
     else
         hipLaunchKernelGGL(k_session_resample_out<false>, dim3(S), dim3(RO_NT), 0, (hipStream_t)stream, out, tail, hold, out_client,
                            bank, o, n, width, T);
+    return check_launch();
+}
+
+// ---- any rate (ABI 31) --------------------------------------------------------------------------------------------------------
+extern "C" int lh_session_resample_out_any(const float* out, float* tail, unsigned* phase, const unsigned* hold, void* out_client,
+                                           int* count, int format, int S, const float* bank_t, int o, int n, int width,
+                                           lh_stream_t stream) {
+    using namespace lh;
+    const void* const bufs[] = {out, tail, phase, hold, out_client, count, bank_t};
+    for (int i = 0; i < 7; ++i)
+        for (int j = i + 1; j < 7; ++j)
+            if (bufs[i] == bufs[j]) return LH_ERR_ARG;         // two nulls among them
+    if ((format != LH_FEED_F32 && format != LH_FEED_S16) || !aligned16(out) || !aligned16(tail) || !aligned16(out_client) ||
+        !aligned_to(phase, 4) || !aligned_to(hold, 4) || !aligned_to(count, 4) || !aligned_to(bank_t, 4) || S <= 0 ||
+        !resample_ratio_ok(o, n, width))
+        return LH_ERR_ARG;
+    int g = HOP, b = o;
+    while (b) { const int t = g % b; g = b; b = t; }           // gcd(128, o)
+    const int K = 2 * width + o, T = K + o + (o + n - 1) / n - 1, P = o / g, Q = HOP / g;
+    const int hop_max = (int)(((long)HOP * n + o - 1) / o);
+    if (T + HOP > RA_XS) return LH_ERR_ARG;
+    if (format == LH_FEED_S16)
+        hipLaunchKernelGGL(k_session_resample_out_any<true>, dim3(S), dim3(RA_NT), 0, (hipStream_t)stream, out, tail, phase, hold,
+                           out_client, count, bank_t, o, n, width, T, P, Q, hop_max);
+    else
+        hipLaunchKernelGGL(k_session_resample_out_any<false>, dim3(S), dim3(RA_NT), 0, (hipStream_t)stream, out, tail, phase, hold,
+                           out_client, count, bank_t, o, n, width, T, P, Q, hop_max);
     return check_launch();
 }
 

@@ -382,7 +382,7 @@ class Net(_cabi.HipHost, nn.Module):
     def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
                               compact: bool = False, row_buckets=None, pace: bool = False, packets: bool = False,
                               fifo_samples: int = 2048, pcm16: bool = False, client_rate: int = 16000, monitor: bool = False,
-                              monitor_ramp: int = 256):
+                              monitor_ramp: int = 256, any_rate: bool = False):
         """The batched streamer with per-listener sessions (slots open, close and fail one at a time): see `SessionStreamer`.
         `enroll_chunks` = n >= 2: slots can also `enroll()` — the device records a slot's next n chunks (128 n samples), the
         enrollment embedder runs beside the chunk loop and the slot opens itself on the result.
@@ -393,11 +393,13 @@ class Net(_cabi.HipHost, nn.Module):
         input — a device FIFO of `fifo_samples` (a power of two >= 256) per slot is re-framed into windows on the device;
         `pcm16`: packets and output are int16.
         `client_rate` (with `packets`): the clients' sample rate, a multiple of 125 Hz; `push` takes and `step` returns PCM at
-        that rate, resampled on the device on the way in and on the way out.
+        that rate, resampled on the device on the way in and on the way out.  `any_rate` lifts the 125 Hz rule: 44100 and its
+        kin are served with a fractional hop (`step` returns `[S, 2, ceil(128 rate / 16000)]`, `last_counts` says how many
+        samples of each row are valid); a multiple of 125 Hz builds the same streamer with or without it.
         `monitor`: every slot has a wet / dry mix (`set_mix`), ramped on the device over `monitor_ramp` 16 kHz samples per
         full swing; `enroll(slot, embedder, passthrough=True)` lets the listener hear the room while they look."""
         return SessionStreamer(self, n_slots, device, use_graph, enroll_chunks, compact, row_buckets, pace, packets,
-                               fifo_samples, pcm16, client_rate, monitor, monitor_ramp)
+                               fifo_samples, pcm16, client_rate, monitor, monitor_ramp, any_rate)
 
     def _enroll_side(self, dev) -> _EnrollSide:
         return _EnrollSide(dev, self.enroll_low_priority)

@@ -476,7 +476,7 @@ class SessionStreamer:
     What a listener hears equals `Resampler(client_rate, 16000)` of their whole stream, served by a 16 kHz packet streamer, then
     `Resampler(16000, client_rate)` of `delay_out` zeros followed by the rows — bit for bit, whatever the packet sizes.  Rates
     are multiples of 125 Hz (a chunk is then a whole number of client samples): 8000, 24000, 32000, 40000, 48000, 96000 ...;
-    44100 is refused — resample such a stream with `Resampler` first.  `fifo_samples`, `buffered`, `ready`, `last_present` and
+    44100 needs `any_rate=True` (below) and is refused without it.  `fifo_samples`, `buffered`, `ready`, `last_present` and
     `BufferError` keep their meaning in 16 kHz samples: the host mirrors the resampler's block arithmetic in integers.
     Added latency: a 16 kHz block is made when its `lookahead_in = width + o - 1` later client samples have been pushed (48 kHz:
     21 samples, 0.44 ms), and the output is `delay_out` 16 kHz samples late (toward 48 kHz: 8 samples, 0.5 ms); the tail of a
@@ -484,6 +484,18 @@ class SessionStreamer:
     The raw ring and the output tail are transport like the FIFO: in no snapshot, untouched by `open`, `close`, `suspend` and
     `resume`; `flush(slot)` and `reset()` clear them, so a flushed slot's stream starts from silence, as torchaudio's left pad
     does.  Enrollment keeps recording the 16 kHz `chunk_in`.
+    Any rate (`client_rate=44100, any_rate=True`; False, the default, and any multiple of 125 Hz with it build exactly the object
+    above, launch for launch): consumer capture and playback run at 44.1 kHz, where a chunk is 352.8 client samples.  The hop is
+    FRACTIONAL: `step()` returns `[S, 2, hop_client]` with `hop_client = ceil(128 client_rate / 16000)` (353), and
+    `last_counts[slot]` — host arithmetic, nothing is read back — says how many leading samples of the slot's row are the next
+    ones of its stream: 352, 353, 353, 353, 353 over a period of 5 live steps, 0 for a held slot (every packet streamer has
+    `last_counts`: `hop_client`, or 128, for a present slot elsewhere); the columns behind are zeros.  The last node is
+    `lh_session_resample_out_any` (include/lookonce_hip.h, "any rate": the slot's phase in the period is a device word, mirrored
+    here), the input side is the one above.  What a listener hears is the same chain, bit for bit, with `delay_out = width + o
+    - 1` 16 kHz samples — 166, 10.4 ms toward 44.1 kHz — on the way out and `lookahead_in` = 457 client samples (10.4 ms) on the
+    way in: about 21 ms in all, the price of keeping torchaudio's block arithmetic to the bit.  The phase is transport like the
+    tail: in no snapshot, zeroed by `flush(slot)` and `reset()` only.  22050, 11025 and 88200 Hz are served alike; a rate that
+    would carry more per slot than 11025 Hz does is refused at construction.
     Monitor (`monitor=True`; False, the default, builds exactly the object above, launch for launch): what a listener hears is
     `wet` x their separated rows + `dry` x their own input.  `set_mix(slot, wet, dry)` (finite, in [0, 1]; any slot, idle ones
     included) holds from the next `step`, `mix_of(slot)` returns the targets.  One more graph node after the end node and ahead of
@@ -517,19 +529,23 @@ class SessionStreamer:
     FEED_F32, FEED_S16, FEED_FLUSH, FEED_ITEM_WORDS = 0, 1, 1, 5                       # LH_FEED_*, lh_feed_item_t
     HOP, WINDOW, COUNTER_MASK = 128, 192, 0xffffffff                                   # samples a chunk consumes / needs
     RATE, RESAMPLE_ITEM_WORDS = 16000, 4                                               # the model's rate; lh_resample_item_t
+    MAX_RATIO, ANY_RATE_STAGE = 4096, 1427                                             # RS_MAX_RATIO; RA_XS of lh_stream.hip
 
     def __init__(self, net: Net, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0, compact: bool = False,
                  row_buckets=None, pace: bool = False, packets: bool = False, fifo_samples: int = 2048, pcm16: bool = False,
-                 client_rate: int = 16000, monitor: bool = False, monitor_ramp: int = 256):
+                 client_rate: int = 16000, monitor: bool = False, monitor_ramp: int = 256, any_rate: bool = False):
         if n_slots < 1:
             raise ValueError("n_slots must be positive")
         if client_rate != self.RATE:
             if not packets:
                 raise ValueError("client_rate is the sample rate of a packet streamer's clients: packets=True")
-            if int(client_rate) != client_rate or client_rate % 125 or not 1000 <= client_rate <= 384000:
+            if int(client_rate) != client_rate or not 1000 <= client_rate <= 384000 or (client_rate % 125 and not any_rate):
                 raise ValueError(f"client_rate must be a multiple of 125 Hz in [1000, 384000] — a 128-sample chunk at 16 kHz is "
                                  f"then a whole number of client samples (8000, 24000, 32000, 48000 ...); {client_rate} is not "
-                                 "(44100 is not either): resample such a stream with resample.Resampler first")
+                                 "(44100 is not either): any_rate=True serves such a rate with a fractional hop")
+            if client_rate % 125 and max(self.RATE, client_rate) // math.gcd(self.RATE, client_rate) > self.MAX_RATIO:
+                raise ValueError(f"client_rate {client_rate}: 16000 / {client_rate} in lowest terms has a term above "
+                                 f"{self.MAX_RATIO}, more than the resampling kernels take")
         if packets and not pace:
             raise ValueError("packets are the input of a paced streamer (the device decides who is present): pace=True")
         if pcm16 and not packets:
@@ -609,6 +625,7 @@ class SessionStreamer:
             if pcm16 and client_rate == self.RATE:
                 self.out16 = torch.zeros(S, net.n_srcs, net.stft_chunk_size, dtype=torch.int16, device=dev)
         self.client_rate, self.hop_client, self._resampling = int(client_rate), self.HOP, client_rate != self.RATE
+        self._fractional = self._resampling and client_rate % 125 != 0      # `any_rate`: a chunk is no whole number of samples
         if self._resampling:
             from .resample import resample_bank
             bank_in, self._w_in, self._o_in, self._n_in = resample_bank(self.client_rate, self.RATE)
@@ -617,6 +634,18 @@ class SessionStreamer:
             self.hop_client = self.HOP * self._o_in // self._n_in
             self.lookahead_in = self._w_in + self._o_in - 1                  # client samples behind a block's first one
             self.delay_out = (self._w_out + 2 * self._o_out - 1) // self._o_out * self._o_out       # 16 kHz samples, D o
+            tail = self._w_out + self.delay_out
+            if self._fractional:                            # lh_session_resample_out_any: d, P, T and hop_max of the header
+                o, n = self._o_out, self._n_out
+                self.hop_client = -(-self.HOP * n // o)
+                self.delay_out = self._w_out + o - 1
+                self._period = o // math.gcd(self.HOP, o)
+                tail = 2 * self._w_out + 2 * o + -(-o // n) - 1
+                if tail + self.HOP > self.ANY_RATE_STAGE:
+                    raise ValueError(f"client_rate {client_rate}: 16000 / {client_rate} = {o} / {n} carries {tail} samples per "
+                                     f"slot and channel; the resample node stages {self.ANY_RATE_STAGE - self.HOP}, what 11025 Hz "
+                                     "needs")
+                bank_out = bank_out.t().contiguous()        # [K][n]: a wave's consecutive phases read consecutive floats
             # a full FIFO's worth of input plus one block's taps: what `push` can leave unconsumed
             self.raw_samples = 256
             while self.raw_samples < self.fifo_samples * self._o_in // self._n_in + self._k_in:
@@ -625,7 +654,9 @@ class SessionStreamer:
             self._raw = torch.zeros(S, net.num_ch, Rin, device=dev)          # a ring per slot and channel, at the client rate
             self._raw_words = torch.zeros(2, S, dtype=torch.int32, device=dev)       # its wr | rd (rd: only FLUSH writes it)
             self._tap0 = -self._w_in & self.COUNTER_MASK                     # a stream's first tap: the left pad lies below 0
-            self._tail = torch.zeros(S, net.n_srcs, self._w_out + self.delay_out, device=dev)
+            self._tail = torch.zeros(S, net.n_srcs, tail, device=dev)
+            if self._fractional:                            # the device's phase and count words; the host mirrors both
+                self._phase, self._count = torch.zeros(2, S, dtype=torch.int32, device=dev)
             self.out_client = torch.zeros(S, net.n_srcs, self.hop_client, dtype=torch.int16 if pcm16 else torch.float32,
                                           device=dev)
             self._bank_in, self._bank_out = bank_in.to(dev), bank_out.to(dev)
@@ -698,7 +729,11 @@ class SessionStreamer:
             if self.monitor:                                # by slot in every flavour, on the rows the end node left
                 lib.call("lh_session_mix", x, P(self.out), P(self._mix[0]), P(self._mix[1]), *(hold or (None,)), self._mix_step,
                          S, stream)
-            if self._resampling:                            # the rows at the client's rate, fp32 or 16-bit
+            if self._fractional:                            # a fractional hop at the client's rate, counted on the device
+                lib.call("lh_session_resample_out_any", P(self.out), P(self._tail), P(self._phase), *hold, P(self.out_client),
+                         P(self._count), self.FEED_S16 if self.pcm16 else self.FEED_F32, S, P(self._bank_out), self._o_out,
+                         self._n_out, self._w_out, stream)
+            elif self._resampling:                          # the rows at the client's rate, fp32 or 16-bit
                 lib.call("lh_session_resample_out", P(self.out), P(self._tail), *hold, P(self.out_client),
                          self.FEED_S16 if self.pcm16 else self.FEED_F32, S, P(self._bank_out), self._o_out, self._n_out,
                          self._w_out, stream)
@@ -733,6 +768,8 @@ class SessionStreamer:
             self.last_present = (False,) * S
         if self._resampling:
             self._raw_wr, self._tap = [0] * S, [self._tap0] * S              # raw samples pushed | next block's first tap
+        if self._fractional:
+            self._phase_of, self._last_counts = [0] * S, (0,) * S            # live steps taken mod P | the last step's counts
         if self.monitor:
             self._targets = [(1.0, 0.0)] * S                # the host's copy of the targets, as fp32 values
             self._mix_posted = True                         # false: a target changed since the last copy
@@ -749,6 +786,9 @@ class SessionStreamer:
         if self._resampling:
             for t in (self._raw, self._raw_words, self._tail, self.out_client):
                 t.zero_()
+        if self._fractional:
+            self._phase.zero_()
+            self._count.zero_()
         if self.compact:
             self._tables.zero_()
             self._tables[1:3].fill_(-1)
@@ -1234,6 +1274,28 @@ class SessionStreamer:
                 rd[s] = (rd[s] + self.HOP) & M
         return took
 
+    def _counted(self, took: tuple) -> tuple:
+        """What lh_session_resample_out_any will count for the slots that took a chunk, c(r + 1) - c(r) client samples at phase
+        r, with their phases a step further."""
+        ph, o, n, P, H = self._phase_of, self._o_out, self._n_out, self._period, self.HOP
+        counts = [0] * self.S
+        for s, t in enumerate(took):
+            if t:
+                r = ph[s]
+                counts[s] = H * (r + 1) * n // o - H * r * n // o
+                ph[s] = (r + 1) % P
+        return tuple(counts)
+
+    @property
+    def last_counts(self) -> tuple:
+        """The valid samples of each slot's row of the last `step` (host arithmetic): 0 for a slot that was held, else 128, the
+        `hop_client` of a fixed-hop client rate, or with `any_rate` the floor or ceil of 128 rate / 16000 that the slot's phase
+        makes it — the columns behind it are zeros."""
+        self._packet_streamer()
+        if self._fractional:
+            return self._last_counts
+        return tuple(self.hop_client if t else 0 for t in self.last_present)
+
     def push(self, packets: dict):
         """packets {slot: CPU tensor [2, n]}, float32 (int16 in a `pcm16` streamer), any n >= 0: the clients' contiguous PCM
         as it arrived since the last call.  One fresh pinned buffer (item table, then the samples), one asynchronous copy
@@ -1268,6 +1330,9 @@ class SessionStreamer:
                     wr16[slot], self._tap[slot] = 0, self._tap0
                     for t in (self._raw[slot], self._tail[slot], self._fifo_words[:, slot]):
                         t.zero_()
+                    if self._fractional:
+                        self._phase_of[slot] = 0
+                        self._phase[slot].zero_()
             at = wr[slot]
             table[i] = (slot, off, n, i32(at), self.FEED_FLUSH if flush else 0)
             if n:
@@ -1375,6 +1440,8 @@ class SessionStreamer:
             if self._flush:                                 # a flush nobody pushed behind travels on its own
                 self.push({})
             self.last_present = self._framed()              # the device frames and holds by itself: no hold word travels
+            if self._fractional:
+                self._last_counts = self._counted(self.last_present)
         elif self.pace:
             held = self._none_held
             if present is not None:

@@ -46,6 +46,10 @@ chunks, Streamer again (drift of the box during the run).  Prints one JSON line;
         present, a chunk's worth of client samples per slot and step (384 at 48 kHz) against the 16 kHz packet streamer fed 128,
         blocks of the two interleaved in one run; `scatter` is the spread of the 16 kHz blocks' p50.  Then the offline
         `Resampler(client_rate, 16000)` on [64, 240000]: bytes read and written over the p50 time against the 8 TB/s of HBM.
+    python scripts/bench_sessions.py --client-rate 44100 --any-rate [--batches 1,64] [--out profiles/any_rate_cost.txt]
+        what the fractional hop costs, in DEVICE time per step, push included as above: everyone present, a step's worth of
+        client samples per slot and step (352 or 353 at 44.1 kHz), the `any_rate=True` streamer against the 48 kHz streamer and
+        the 16 kHz packet streamer, blocks of the three interleaved in one run; `scatter` is the spread of the 16 kHz blocks' p50.
     python scripts/bench_sessions.py --monitor [--batches 1,64] [--out profiles/monitor_cost.txt]
         what the monitor mix node costs, in DEVICE time per chunk as above, every slot open, the same streamer built with
         `monitor=False` and with `monitor=True`, blocks of the two interleaved in one run, in three states of the node: (a) settled
@@ -559,6 +563,79 @@ def client_rate_bench(net, args):
             f.write(text + "\n")
 
 
+def any_rate_bench(net, args):
+    """`--client-rate 44100 --any-rate`: the fractional-hop streamer against the 48 kHz streamer and the 16 kHz packet streamer,
+    blocks of the three interleaved in one run."""
+    rate, reps, N = args.client_rate, 4, 80000
+    lines = [f"any rate, client rate {rate} Hz (any_rate=True), device time per step (HIP events around push + step), everyone "
+             f"present, {args.steps} steps per figure in {reps} interleaved blocks after {args.warmup} warm-up; the yardsticks are the "
+             f"16 kHz packet streamer and the 48 kHz streamer of the same run; the bar for a difference is three times the scatter of "
+             f"the 16 kHz blocks' p50"]
+    for B in [int(b) for b in args.batches.split(",")]:
+        emb = synth.batch(list(range(B)), N)["embedding_gt"][:, 0].to(DEV)
+        mk = net.make_session_streamer
+        arms = {"16 kHz": (mk(B, DEV, pace=True, packets=True), 16000),
+                "48 kHz": (mk(B, DEV, pace=True, packets=True, client_rate=48000), 48000),
+                f"{rate} Hz": (mk(B, DEV, pace=True, packets=True, client_rate=rate, any_rate=True), rate)}
+        # the same kind of signal read at each rate: what is timed does not depend on the samples
+        hosts = {k: synth.batch(list(range(B)), N * r // 16000)["mixture"].pin_memory() for k, (_, r) in arms.items()}
+        pos, step_no = {k: 0 for k in arms}, {k: 0 for k in arms}
+        for k, (ss, r) in arms.items():
+            for s in range(B):
+                ss.open(s, emb[s])
+            # the look-ahead of the window and of the resampler, and one input block of slack: a step's samples arrive as
+            # floor((i + 1) 128 r / 16000) - floor(i 128 r / 16000), while the 16 kHz side is made in whole blocks
+            first = 64 * r // 16000 + (ss.lookahead_in + ss._o_in if r != 16000 else 0)
+            ss.push({s: hosts[k][s, :, :first] for s in range(B)})
+            pos[k] = first
+
+        def run(k, n):
+            (ss, r), host, ms = arms[k], hosts[k], []
+            for _ in range(n):
+                i = step_no[k]
+                per = 128 * (i + 1) * r // 16000 - 128 * i * r // 16000
+                step_no[k] = i + 1
+                at = pos[k] if pos[k] + per <= host.shape[-1] else 0
+                packets = {s: host[s, :, at:at + per].contiguous() for s in range(B)}
+                pos[k] = at + per
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ss.push(packets)
+                ss.step()
+                e1.record()
+                e1.synchronize()
+                assert all(ss.last_present), (k, i)
+                ms.append(e0.elapsed_time(e1))
+            return ms
+
+        for k in arms:
+            run(k, args.warmup)
+        ms, p50s = {k: [] for k in arms}, []
+        for rep in range(reps):
+            for k in arms:
+                blk = run(k, args.steps // reps)
+                ms[k] += blk
+                if k == "16 kHz":
+                    p50s.append(pct(blk, 0.5))
+        torch.cuda.synchronize()
+        assert all(ss.faults() == [] and len(ss.active) == B for ss, _ in arms.values())
+        r = {k: stats(v) for k, v in ms.items()}
+        scatter = max(p50s) - min(p50s)
+        name = f"{rate} Hz"
+        lines.append(f"S={B:3d}   " + "   ".join(f"{k}: p50 {r[k]['p50_ms']:.4f} p99 {r[k]['p99_ms']:.4f} ms" for k in arms))
+        for k in ("16 kHz", "48 kHz"):
+            cost = r[name]["p50_ms"] - r[k]["p50_ms"]
+            lines.append(f"S={B:3d}   {name} minus {k}: {1e3 * cost:+.1f} us ({100.0 * cost / r[k]['p50_ms']:+.1f} %), scatter of the "
+                         f"16 kHz blocks {1e3 * scatter:.1f} us: {'WITHIN' if abs(cost) <= 3 * scatter else 'NOT within'} three times "
+                         f"the scatter")
+        del arms
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def monitor_bench(net, args):
     reps = 4
     lines = [f"monitor mix cost, device time per chunk (HIP events around each replay), every slot open, {args.steps} steps per "
@@ -705,6 +782,7 @@ def main():
     ap.add_argument("--suspend-many", action="store_true")
     ap.add_argument("--packets", action="store_true")
     ap.add_argument("--client-rate", type=int, default=0)
+    ap.add_argument("--any-rate", action="store_true")
     ap.add_argument("--monitor", action="store_true")
     ap.add_argument("--many", default="1,8,64")
     ap.add_argument("--tiles", default="")
@@ -734,6 +812,8 @@ def main():
         return suspend_many_bench(net, args)
     if args.packets:
         return packets_bench(net, args)
+    if args.client_rate and args.any_rate:
+        return any_rate_bench(net, args)
     if args.client_rate:
         return client_rate_bench(net, args)
     if args.monitor:
