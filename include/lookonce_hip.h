@@ -73,8 +73,9 @@ int lh_selftest_fp16_subnormal(lh_stream_t stream);
  *                 the image (weights.py pack_block), the kernel only standardises x; ln_w/ln_b are ignored  */
 enum { LH_GEMM_F32 = 0, LH_GEMM_F16X3 = 1 };
 
-/* ABI version of this header (29); bumped on any signature or buffer-contract change (29: the LayerNorm eps behind the bias
- * of lh_qkv_proj_ln*, lh_proj_ln_res*, lh_emb_attn_block and lh_emb_head, below). */
+/* ABI version of this header (32); bumped on any signature or buffer-contract change (29: the LayerNorm eps behind the bias
+ * of lh_qkv_proj_ln*, lh_proj_ln_res*, lh_emb_attn_block and lh_emb_head, below; 32: streaming chunks of several frames —
+ * ring_pos of lh_qkv_proj_ln* for T <= 16, lh_local_attn_ring, lh_ring_advance_by). */
 int lh_abi_version(void);
 
 /* Launch-shape tuning knobs (benchmark A/B only; 0 = automatic): key 0 = sequences-per-workgroup/16 of the
@@ -223,9 +224,23 @@ int lh_linear_res(const float* h, const void* w_pk, const float* bias, const flo
  *          variance: PReLU is positively homogeneous and a power of two exact, so LN_{eps 4^k}(2^k z) = LN_eps(z).
  *   slopes [3] PReLU slopes (Q,K,V);  lnq_w/b, lnk_w/b [608] = the 582 affine values zero-padded;  lnv_w/b [1552]
  *   q, kx, vx  split-precision rows (above)
- *   ring_pos   NULL, or (T = 1 only) a device counter: the K / V row goes to slot (*ring_pos mod 50) of a persistent
+ *   ring_pos   NULL, or (T = 1) a device counter: the K / V row goes to slot (*ring_pos mod 50) of a persistent
  *              50-row ring instead of row 49 — rows 0..49 are then exactly the window of the one query frame, in
- *              rotated order (softmax and P.V are order-free), and no history row ever has to be moved
+ *              rotated order (softmax and P.V are order-free), and no history row ever has to be moved;
+ *              or (ABI 32, 2 <= T <= 16, the whole clip only) the position word of a ring of 49 + T rows, "frames per
+ *              chunk" below.  T > 16 with ring_pos: LH_ERR_ARG.
+ *
+ * Frames per chunk (ABI 32).  A streamer that serves m frames per chunk (1 <= m <= 16) keeps, per block and (batch, head), a
+ * ring of R = 49 + m rows: the FIRST R rows of kx / vx buffers of m + 49 + LH_KV_PAD_ROWS rows — the shape lh_local_attn
+ * expects for T = m.  The 48 rows behind the ring are zeroed once by the caller and never written.  `pos`, a device word in
+ * [0, R), names the slot that frame 0 of the next chunk goes to:
+ *   write   frame j of the chunk (j < m) goes to slot ((unsigned)pos + j) mod R          (lh_qkv_proj_ln, ring_pos = &pos)
+ *   read    logical history-extended row n (n = 0..48: history, oldest first; n = 49 + j: the chunk's frame j) is physical
+ *           row ((unsigned)pos + m + n) mod R for n < R.  Rows n >= R, which the tile over-reads without needing them, are
+ *           physical row n: the zero pad rows, and R >= 50 keeps every such read inside the buffer (lh_local_attn_ring)
+ *   after   pos = (pos + m) mod R                                                         (lh_ring_advance_by)
+ * With m = 1 this is the 50-row ring above: R = 50, write at pos mod 50; every row is then in the one frame's window and
+ * lh_local_attn itself serves the read.
  */
 int lh_qkv_proj_ln(const float* y, const void* w_pk, const float* bias, const float* slopes, const float* lnq_w,
                    const float* lnq_b, const float* lnk_w, const float* lnk_b, const float* lnv_w,
@@ -250,6 +265,12 @@ int lh_qkv_proj_ln_rows(const float* y, const void* w_pk, const float* bias, con
  *   merged [B][T][4][97][16]   merged[b][t][h][f][v] = O[b*4+h][t][f*16+v]   (head-major frame slabs)
  */
 int lh_local_attn(const void* q, const void* kx, const void* vx, float* merged, int B, int T, lh_stream_t stream);
+/* lh_local_attn on a ring (ABI 32, "frames per chunk" above): 1 <= T <= 16 query frames whose history-extended rows are read
+ * through the read rule; *ring_pos is the value the lh_qkv_proj_ln launch of the same chunk saw.  The row map goes into the
+ * row addresses only: the output is bit for bit that of lh_local_attn on the same rows laid out contiguously.  Launch
+ * geometry of lh_local_attn for T <= 16.  LH_ERR_ARG: a null pointer, T < 1 or T > 16. */
+int lh_local_attn_ring(const void* q, const void* kx, const void* vx, float* merged, const int* ring_pos, int B, int T,
+                       lh_stream_t stream);
 
 /* A.3.4  streaming state <-> history rows (tfgridnet_causal.py:553-562).  The reference carries the last 49 K / V
  * rows as fp32 state:  lh_ring_pack writes k_buf [B*4][49][582] / v_buf [B*4][49][1552] into rows 0..48 of kx / vx
@@ -261,6 +282,9 @@ int lh_ring_unpack(const void* kx, const void* vx, float* k_buf, float* v_buf, i
  * stream order — one node of the captured per-chunk graph (the reference has no counterpart: it shifts K_buf / V_buf by
  * one row per chunk, tfgridnet_causal.py:553-562).  modulo in [1, 2^30]. */
 int lh_ring_advance(int* ring_pos, int modulo, lh_stream_t stream);
+/* ... by `step` slots (ABI 32: a chunk of `step` frames on a ring of `modulo` rows): *ring_pos = (*ring_pos + step) mod modulo,
+ * 1 <= step <= modulo <= 2^30. */
+int lh_ring_advance_by(int* ring_pos, int step, int modulo, lh_stream_t stream);
 /* Per-row form (ABI 19): pos[r] = (write_pos[r] + 1) mod modulo where write_pos[r] >= 0, untouched otherwise, r < n_rows.
  * The only writer of a paced host's ring positions apart from a row move.  LH_ERR_ARG: null, pos == write_pos, n_rows < 1. */
 int lh_ring_advance_rows(int* pos, const int* write_pos, int modulo, int n_rows, lh_stream_t stream);

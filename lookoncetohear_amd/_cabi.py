@@ -11,7 +11,7 @@ from ctypes import c_double, c_float, c_int, c_ulonglong, c_void_p
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_PKG, "_lookonce_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 _P, _I = c_void_p, c_int
 # name -> argtypes; mirrors include/lookonce_hip.h one to one (tests/test_cabi_symbols.py checks both ways)
@@ -34,6 +34,9 @@ SIGNATURES = {
     "lh_ring_pack": [_P] * 4 + [_I, _I, _P],
     "lh_ring_unpack": [_P] * 4 + [_I, _I, _P],
     "lh_ring_advance": [_P, _I, _P],
+    # frames per chunk (ABI 32): the attention of a chunk of up to 16 frames on its K / V ring, Streamer(frames_per_chunk=m)
+    "lh_local_attn_ring": [_P] * 5 + [_I, _I, _P],
+    "lh_ring_advance_by": [_P, _I, _I, _P],
     # streaming sessions (ABI 16): first / last node of a SessionStreamer's per-chunk graph
     "lh_session_begin": [_P, _I, _P, _P, _P, _P, _I, _P],
     "lh_session_end": [_P, _I, _P, _P, _P, _P, _P, _I, _P],

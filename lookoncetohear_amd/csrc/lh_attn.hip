@@ -38,10 +38,20 @@ __device__ unsigned long long lh_attn_trace_buf[16];
 #else
 #define AT_STAMP(k) do { } while (0)
 #endif
-template <int MQ, int RING, int TQ = 16 * MQ, int POL = 0>      // POL: cache policy of Q, K, V and merged (lh_cachepol.h)
+// RMAP (ABI 32, lh_local_attn_ring: a streaming chunk of T <= 16 frames, one tile, t0 = 0) is a template flag: the first
+// R = HIST + T rows of kx / vx are a persistent ring and logical history-extended row n lives in physical row
+// (*ring_pos + T + n) mod R for n < R; rows n >= R (read, never needed) are the zero pad rows, physical row n (R >= 50 keeps
+// them inside the buffer).  The map goes into the K row offsets and the V row bases, computed once per lane; the loops, the
+// MFMA order and so the bits are those of the contiguous kernel.  The last argument is the ring position word — an empty
+// struct in every other instantiation, which stay the code they were.
+struct NoRing {};
+template <bool RMAP> struct RingWord { typedef NoRing type; };
+template <> struct RingWord<true> { typedef const int* type; };
+template <int MQ, int RING, int TQ = 16 * MQ, bool RMAP = false, int POL = 0>      // POL: cache policy of Q, K, V and merged (lh_cachepol.h)
 __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restrict__ q, const _Float16* __restrict__ kx,
                                                        const _Float16* __restrict__ vx, float* __restrict__ merged,
-                                                       int BH, int T, int ntt, int tw0, int tend) {
+                                                       int BH, int T, int ntt, int tw0, int tend,
+                                                       typename RingWord<RMAP>::type ring_pos) {
     // TQ query frames per workgroup in MQ MFMA row tiles (TQ = 16 MQ, or 40 in 3 tiles: 625 frames are then 16 tiles
     // per (batch, head), 2048 workgroups at batch 32 = exactly four rounds of the 512 resident workgroups; or 79 in 5
     // tiles: 8 tiles per (batch, head), two rounds — attn_form below)
@@ -64,6 +74,7 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
     static_assert(!OWN || (MQ == 5 && NKT == 8 && NKEYS == PKS * 32), "wave-owned products: 4 x 5 + 4 of the band");
     // frames of a pulled-back tile < NK - HIST - KV_PAD <= NK - KBACK - HIST = the first query that sees key NK - KBACK
     static_assert(KBACK <= KV_PAD && KBACK % 32 == 0, "a pulled-back tile has no query that sees the rows it replaces");
+    static_assert(!RMAP || (MQ == 1 && TQ == 16), "the ring map serves the one-tile form");
     __shared__ __attribute__((aligned(16))) float sp[OWN ? 1 : 4][TQ][NB];  // (per-wave partial) scores, band-relative columns (d, l15)
     __shared__ __attribute__((aligned(16))) _Float16 ph[16 * MQ][PP];
     __shared__ __attribute__((aligned(16))) _Float16 pl[16 * MQ][PP];
@@ -78,6 +89,20 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
     const _Float16* kb = kx + ((long)bh * TKP + t0) * LDQKH;
     const _Float16* vb = vx + ((long)bh * TKP + t0) * LDVH;
     const int kback = t0 + NK - 1 > T + HIST + KV_PAD - 1 ? KBACK : 0;      // scalar: rows the last 32 key rows are pulled back by
+    // RMAP: physical row of logical row n (t0 = 0).  rbase = (*ring_pos + T) mod R is scalar; unsigned: never before the ring
+    int rrows = 0, rbase = 0;
+    if constexpr (RMAP) {
+        rrows = HIST + T;
+        rbase = (int)(((unsigned)*ring_pos + (unsigned)T) % (unsigned)rrows);
+    }
+    auto xrow = [&](int n) -> int {
+        if constexpr (RMAP) {
+            const int p = rbase + n;
+            return n >= rrows ? n : p >= rrows ? p - rrows : p;
+        } else {
+            return n;
+        }
+    };
 
     AT_STAMP(0);
     // ---- scores: S[i][n] = <Q[t0+i], Kx[t0+n]>
@@ -159,7 +184,7 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
 #pragma unroll
         for (int mq = 0; mq < MQ; ++mq) qoff[mq] = min(t0 + mq * 16 + l15, tend - 1) * LDQKH + g4 * 16;
 #pragma unroll
-        for (int nt = 0; nt < NKT; ++nt) koff[nt] = (nt * 16 + l15) * LDQKH + g4 * 16;
+        for (int nt = 0; nt < NKT; ++nt) koff[nt] = xrow(nt * 16 + l15) * LDQKH + g4 * 16;
         constexpr int NIT = (AT_KSTEPS + 3) / 4;       // 5 (wave 3 runs 4)
         Frag fq[2][MQ], fk[2][NKT];
         auto fetch = [&](int it, Frag (&dq)[MQ], Frag (&dk)[NKT]) {
@@ -285,7 +310,7 @@ __global__ void __launch_bounds__(256, 2) k_local_attn(const _Float16* __restric
                 }
                 // OWN: the row is a scalar base and the lane's part one 32-bit offset per column group (as 64-bit lane addresses
                 // the 32 rows of a column group were hoisted out of the loop: 64 registers, and the kernel spilled)
-                const _Float16* p = OWN ? (vb + (32 * ks + j - (ks == 3 ? kback : 0)) * LDVH) + (unsigned)(8 * g4 * LDVH + qc) : vb + r * LDVH + qc;
+                const _Float16* p = OWN ? (vb + (32 * ks + j - (ks == 3 ? kback : 0)) * LDVH) + (unsigned)(8 * g4 * LDVH + qc) : vb + xrow(r) * LDVH + qc;
                 VQuad v;
                 if constexpr (cp::nt(POL, cp::ATT_V_LD)) {        // one 16-byte access, as the plain pair of 8-byte ones is merged into
                     const f16x8 hl = cp::ld_h8<POL, cp::ATT_V_LD>(p);
@@ -500,25 +525,39 @@ extern "C" int lh_local_attn_win(const void* q, const void* kx, const void* vx, 
     // shape is the streaming chunk's and stays plain.
     const bool pol = cp::nt_on((long)B * Tc * NF * C * 4);
     if (mq == 1)
-        hipLaunchKernelGGL((k_local_attn<1, 3, 16, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<1, 3, 16, false, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     else if (mq == 5 && pol)
-        hipLaunchKernelGGL((k_local_attn<5, 2, 79, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<5, 2, 79, false, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     else if (mq == 5)
-        hipLaunchKernelGGL((k_local_attn<5, 2, 79, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<5, 2, 79, false, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     else if (mq == 3 && pol)
-        hipLaunchKernelGGL((k_local_attn<3, 2, 40, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<3, 2, 40, false, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     else if (mq == 3)
-        hipLaunchKernelGGL((k_local_attn<3, 2, 40, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<3, 2, 40, false, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     else if (pol)
-        hipLaunchKernelGGL((k_local_attn<2, 2, 32, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<2, 2, 32, false, 1>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     else
-        hipLaunchKernelGGL((k_local_attn<2, 2, 32, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc);
+        hipLaunchKernelGGL((k_local_attn<2, 2, 32, false, 0>), grid, dim3(256), 0, (hipStream_t)stream, qh, kh, vh, merged, BH, Tfull, ntt, t0, t0 + Tc, NoRing{});
     return check_launch();
 }
 
 extern "C" int lh_local_attn(const void* q, const void* kx, const void* vx, float* merged, int B, int T,
                              lh_stream_t stream) {
     return lh_local_attn_win(q, kx, vx, merged, B, T, 0, T, stream);
+}
+
+// lh_local_attn for a streaming chunk of T <= 16 frames on the persistent ring (include/lookonce_hip.h, "frames per chunk"):
+// the launch geometry of the one-tile form above, the ring map instantiation
+extern "C" int lh_local_attn_ring(const void* q, const void* kx, const void* vx, float* merged, const int* ring_pos, int B, int T,
+                                  lh_stream_t stream) {
+    using namespace lh;
+    if (!q || !kx || !vx || !merged || !ring_pos || B <= 0 || T < 1 || T > 16) return LH_ERR_ARG;
+    const int BH = B * NH;
+    const int bh8 = (BH + 7) / 8 * 8;
+    const dim3 grid(bh8, bh8 <= 64 ? 7 : 1);      // ntt = 1
+    hipLaunchKernelGGL((k_local_attn<1, 3, 16, true, 0>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)q,
+                       (const _Float16*)kx, (const _Float16*)vx, merged, BH, T, 1, 0, T, ring_pos);
+    return check_launch();
 }
 
 extern "C" int lh_ring_pack(const float* k_buf, const float* v_buf, void* kx, void* vx, int B, int T,
@@ -543,6 +582,18 @@ __global__ void k_ring_advance(int* pos, int modulo) {
 extern "C" int lh_ring_advance(int* ring_pos, int modulo, lh_stream_t stream) {
     if (!ring_pos || modulo < 1 || modulo > (1 << 30)) return LH_ERR_ARG;
     hipLaunchKernelGGL(lh::k_ring_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, ring_pos, modulo);
+    return lh::check_launch();
+}
+
+namespace lh {
+__global__ void k_ring_advance_by(int* pos, int step, int modulo) {
+    *pos = (int)(((unsigned)*pos + (unsigned)step) % (unsigned)modulo);
+}
+}  // namespace lh
+
+extern "C" int lh_ring_advance_by(int* ring_pos, int step, int modulo, lh_stream_t stream) {
+    if (!ring_pos || step < 1 || step > modulo || modulo > (1 << 30)) return LH_ERR_ARG;
+    hipLaunchKernelGGL(lh::k_ring_advance_by, dim3(1), dim3(1), 0, (hipStream_t)stream, ring_pos, step, modulo);
     return lh::check_launch();
 }
 

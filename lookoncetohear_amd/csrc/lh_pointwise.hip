@@ -246,7 +246,10 @@ __device__ __forceinline__ void qkv_products(const _Float16* ahi, const _Float16
 // code it was.  With ROWS (T = Tc = 1, tw0 = 0) `ring_pos` is write_pos[B]: frame b writes its K / V rows into ring slot
 // write_pos[b], a negative entry writes neither (a held or idle row: its Q row is still written, from the zero-gated input).
 // POL (lh_cachepol.h): 0 = plain accesses, 1 = the frame load and the Q / K / V stores as the stream table says
-template <bool ROWS, int POL = 0>
+// RINGM (ABI 32: a streaming chunk of 2 <= T <= 16 frames on a persistent ring of R = HIST + T rows, whole clip) is a flag
+// in the same manner: frame t of the chunk writes its K / V rows into slot (*ring_pos + t) mod R.  The modulo is taken once
+// in front of the frame loop; per frame the slot is one scalar add, compare and select (t is wave-uniform).
+template <bool ROWS, bool RINGM = false, int POL = 0>
 __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict__ y, const _Float16* __restrict__ w_pk,
                                                      const float* __restrict__ bias, const float* __restrict__ slopes,
                                                      const float* __restrict__ lnq_w, const float* __restrict__ lnq_b,
@@ -304,7 +307,9 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
     // K / V row of frame t: HIST + t behind the history rows — or, for a one-frame chunk on a persistent ring
     // (ring_pos != NULL, T = 1), slot (*ring_pos mod 50): the 50 rows are then exactly the attention window, in
     // rotated order, which softmax and P.V do not care about
-    const int krow0 = ROWS ? 0 : ring_pos ? (int)((unsigned)*ring_pos % (unsigned)WIN) : HIST;   // unsigned: never before the ring
+    static_assert(!(ROWS && RINGM), "per-row positions are one-frame chunks");
+    const int krow0 = ROWS ? 0 : RINGM ? (int)((unsigned)*ring_pos % (unsigned)(HIST + T))
+                           : ring_pos ? (int)((unsigned)*ring_pos % (unsigned)WIN) : HIST;   // unsigned: never before the ring
     for (int fr = blockIdx.x; fr < nframes; fr += gridDim.x) {      // grid-stride over frames (b*T + t)
         const int b = fr / Tc, t = tw0 + fr % Tc;
         QKV_STAMP(0);
@@ -337,9 +342,11 @@ __global__ void __launch_bounds__(256, 2) k_qkv_proj_ln(const float* __restrict_
         // ROWS: T = 1, fr = b; the row's own slot, wave-uniform
         const int wp = ROWS ? ring_pos[fr] : 0;
         const int krow = ROWS ? (int)((unsigned)wp % (unsigned)WIN) : krow0;
+        // RINGM: slot (pos + t) mod R = krow + tk, scalar
+        const int tk = RINGM ? (krow + t >= HIST + T ? t - (HIST + T) : t) : t;
         _Float16* qrow = q + (bh * T + t) * LDQKH;
-        _Float16* krow_p = kx + (bh * tkp + krow + t) * LDQKH;
-        _Float16* vrow = vx + (bh * tkp + krow + t) * LDVH;
+        _Float16* krow_p = kx + (bh * tkp + krow + tk) * LDQKH;
+        _Float16* vrow = vx + (bh * tkp + krow + tk) * LDVH;
         // `fr >> 30` is always 0 but ties the lane index to the loop variable: without it LICM hoists every slot address
         // of the three rows (and V's affine) out of the persistent frame loop and the kernel spills
         const int ln = lane + (fr >> 30);
@@ -669,16 +676,21 @@ extern "C" int lh_qkv_proj_ln_win(const float* y, const void* w_pk, const float*
                                   int B, int T, int t0, int Tc, lh_stream_t stream) {
     using namespace lh;
     if (!y || !w_pk || !bias || !slopes || !lnq_w || !lnq_b || !lnk_w || !lnk_b || !lnv_w || !lnv_b || !q || !kx ||
-        !vx || B <= 0 || T <= 0 || (ring_pos && T != 1) || t0 < 0 || Tc <= 0 || t0 + Tc > T)
+        !vx || B <= 0 || T <= 0 || (ring_pos && (T > 16 || t0 != 0 || Tc != T)) || t0 < 0 || Tc <= 0 || t0 + Tc > T)
         return LH_ERR_ARG;
     const int nframes = B * Tc;
+    // a streaming chunk of several frames on its ring (ABI 32): a launch of its own, plain accesses like the one-frame chunk
+    if (ring_pos && T > 1)
+        hipLaunchKernelGGL((k_qkv_proj_ln<false, true, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream,
+                           y, (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
+                           (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
     // cache policy by the footprint of the launch's largest stream (the frames of x; V is as large): lh_cachepol.h
-    if (cp::nt_on((long)nframes * NF * C * 4))
-        hipLaunchKernelGGL((k_qkv_proj_ln<false, 1>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
+    else if (cp::nt_on((long)nframes * NF * C * 4))
+        hipLaunchKernelGGL((k_qkv_proj_ln<false, false, 1>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
                            (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
                            (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
     else
-        hipLaunchKernelGGL((k_qkv_proj_ln<false, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
+        hipLaunchKernelGGL((k_qkv_proj_ln<false, false, 0>), dim3(nframes < 512 ? nframes : 512), dim3(256), 0, (hipStream_t)stream, y,
                            (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
                            (_Float16*)kx, (_Float16*)vx, T, nframes, ring_pos, Tc, t0);
     return check_launch();
@@ -700,7 +712,7 @@ extern "C" int lh_qkv_proj_ln_rows(const float* y, const void* w_pk, const float
     if (!y || !w_pk || !bias || !slopes || !lnq_w || !lnq_b || !lnk_w || !lnk_b || !lnv_w || !lnv_b || !q || !kx || !vx ||
         !write_pos || B <= 0)
         return LH_ERR_ARG;
-    hipLaunchKernelGGL((k_qkv_proj_ln<true, 0>), dim3(B < 512 ? B : 512), dim3(256), 0, (hipStream_t)stream, y,
+    hipLaunchKernelGGL((k_qkv_proj_ln<true, false, 0>), dim3(B < 512 ? B : 512), dim3(256), 0, (hipStream_t)stream, y,
                        (const _Float16*)w_pk, bias, slopes, lnq_w, lnq_b, lnk_w, lnk_b, lnv_w, lnv_b, (_Float16*)q,
                        (_Float16*)kx, (_Float16*)vx, 1, B, write_pos, 1, 0);
     return check_launch();

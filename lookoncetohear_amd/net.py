@@ -375,9 +375,10 @@ class Net(_cabi.HipHost, nn.Module):
             y = y[..., :-mod]
         return y
 
-    def make_streamer(self, batch_size: int, device, use_graph: bool = True):
-        """Chunked real-time front end (BASELINE configs[1]): see `Streamer`."""
-        return Streamer(self, batch_size, device, use_graph)
+    def make_streamer(self, batch_size: int, device, use_graph: bool = True, frames_per_chunk: int = 1):
+        """Chunked real-time front end (BASELINE configs[1]): see `Streamer`.  `frames_per_chunk` = m in 1..16: a `step` takes
+        128 m + 64 samples and returns 128 m, at an algorithmic latency of 8 m + 4 ms."""
+        return Streamer(self, batch_size, device, use_graph, frames_per_chunk)
 
     def make_session_streamer(self, n_slots: int, device, use_graph: bool = True, enroll_chunks: int = 0,
                               compact: bool = False, row_buckets=None, pace: bool = False, packets: bool = False,
@@ -1062,9 +1063,12 @@ class Net(_cabi.HipHost, nn.Module):
 
     def _stream_chunk(self, x, gain, sin: dict, sout: dict, rings, pos, y, pk: dict, ws: dict, flag=None,
                       keep_nonfinite: int = 0, write_pos=None):
-        """One chunk of ONE frame for `Streamer`: the launches of `_separate` with every state tensor read from `sin` and
-        written to `sout` (preallocated), the K / V history in per-block persistent rings, the speaker gain given.
-        `pk` / `ws`: the packed weights and the T=1 workspace, OWNED by the caller — a captured graph holds raw pointers
+        """One chunk of T = m frames (x [B, 2, 128 m + 64]; m = 1 but for a `Streamer` with `frames_per_chunk`) for `Streamer`:
+        the launches of `_separate` with every state tensor read from `sin` and written to `sout` (preallocated), the K / V
+        history in per-block persistent rings of 49 + m rows, the speaker gain given.  m > 1: the ring forms of the Q / K / V
+        and attention launches (include/lookonce_hip.h, "frames per chunk") and, for the intra pair, the kernel `_separate`
+        picks at B m frames.
+        `pk` / `ws`: the packed weights and the (B, m) workspace, OWNED by the caller — a captured graph holds raw pointers
         into them, so they must not be the entries `_weights` / `_workspace` may replace or evict later.
         `keep_nonfinite`: lh_deconv_istft's switch — 0 for `Streamer` (silence, not NaN, reaches a listener), 1 for
         `SessionStreamer`, whose own last kernel looks at the samples and silences the slot.
@@ -1075,7 +1079,8 @@ class Net(_cabi.HipHost, nn.Module):
         hop, nfft = self.stft_chunk_size, self.nfft
         Bn, _, n = x.shape
         T = (n - nfft) // hop + 1
-        assert T == 1 and n == nfft, "the streaming path takes chunks of stft_chunk_size + stft_pad_size samples"
+        if T < 1 or T > 16 or n != (T - 1) * hop + nfft or (write_pos is not None and T != 1):
+            raise ValueError(f"the streaming path takes chunks of {hop} m + {nfft - hop} samples, m in 1..16, got {n}")
         F_, H_ = self.n_freqs, self.hidden
         st = self._stream(dev)
         P = lambda t: t.data_ptr()
@@ -1085,8 +1090,12 @@ class Net(_cabi.HipHost, nn.Module):
         for i in range(self.n_blocks):
             bp = pk["blocks"][i]
             kx, vx = rings[i]
-            lib.call("lh_intra_stream", P(xa), P(bp["intra_s_wih"]), P(bp["intra_s_b"]), P(bp["intra_s_whh"]), P(hbuf),
-                     Bn * T, st)
+            if Bn * T <= self.stream_intra_max_frames or T == 1:
+                lib.call("lh_intra_stream", P(xa), P(bp["intra_s_wih"]), P(bp["intra_s_b"]), P(bp["intra_s_whh"]), P(hbuf),
+                         Bn * T, st)
+            else:       # more frames than one workgroup per (frame, direction) finds CUs for: the tiled kernel, as `_blocks_whole`
+                lib.call("lh_ln_lstm_intra", P(xa), P(bp["intra_ln_w"]), P(bp["intra_ln_b"]), P(bp["intra_w16"]),
+                         P(bp["intra_b16"]), P(hbuf), Bn * T, 1, st)
             lib.call("lh_linear_res", P(hbuf), P(bp["intra_lin_w"]), P(bp["intra_lin_b"]), P(xa), P(xb), Bn * T * F_,
                      2 * H_, st)
             lib.call("lh_inter_block", P(xb), P(bp["inter_w8"]), P(bp["inter_b16"]), P(bp["inter_lin_wu"]),
@@ -1099,7 +1108,10 @@ class Net(_cabi.HipHost, nn.Module):
                 lib.call("lh_qkv_proj_ln_rows", P(xc), P(bp["qkv_w"]), P(bp["qkv_b"]), P(bp["qkv_slopes"]), P(bp["lnq_w"]),
                          P(bp["lnq_b"]), P(bp["lnk_w"]), P(bp["lnk_b"]), P(bp["lnv_w"]), P(bp["lnv_b"]), P(ws["q"]),
                          P(kx), P(vx), P(write_pos), Bn, st)
-            lib.call("lh_local_attn", P(ws["q"]), P(kx), P(vx), P(xb), Bn, T, st)
+            if T == 1:
+                lib.call("lh_local_attn", P(ws["q"]), P(kx), P(vx), P(xb), Bn, T, st)
+            else:
+                lib.call("lh_local_attn_ring", P(ws["q"]), P(kx), P(vx), P(xb), P(pos), Bn, T, st)
             g = gain if (i == 0 and self.n_blocks > 1) else None
             lib.call("lh_proj_ln_res", P(xb), P(bp["proj_w"]), P(bp["proj_b"]), P(bp["proj_slope"]),
                      P(bp["proj_ln_w"]), P(bp["proj_ln_b"]), P(xc), P(g) if g is not None else None, P(xa), Bn, T, st)

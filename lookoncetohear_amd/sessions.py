@@ -30,26 +30,34 @@ class Streamer:
       * the speaker gain LayerNorm(Linear(embedding)) is computed once in `set_embedding`.
     `step()` is: copy the chunk in, replay a graph, hand back the output buffer (a view that the next `step`
     overwrites).  `use_graph=False` runs the same launches eagerly (also what the capture warm-up does).
+    `frames_per_chunk` = m in 1..16 (DESIGN.md §5 "Frames per chunk"): a chunk is m frames — 128 m new samples plus the 64 of
+    look-ahead in, 128 m out — for hosts that can afford 8 m + 4 ms of algorithmic latency and want the per-chunk launch chain
+    paid once per m frames.  The rings are then 49 + m rows; the m new rows go to slots pos .. pos + m - 1 (mod 49 + m) and the
+    attention kernel reads the ring in place through a row map (`lh_local_attn_ring`), so still nothing is moved.  m = 1 is the
+    object described above, launch for launch.
     Measured (MI355X, batch 1): 0.68 ms per chunk with the generic `predict` path captured in one graph, see DESIGN.md.
     """
 
-    def __init__(self, net: Net, batch_size: int, device, use_graph: bool = True):
+    def __init__(self, net: Net, batch_size: int, device, use_graph: bool = True, frames_per_chunk: int = 1):
         if net.gemm_mode != "f16x3" or not net.fuse_linear:
             raise ValueError("Streamer runs the split-precision fused kernels (LOOKONCE_GEMM=f16x3, LOOKONCE_FUSE=1)")
+        if isinstance(frames_per_chunk, bool) or not isinstance(frames_per_chunk, int) or not 1 <= frames_per_chunk <= 16:
+            raise ValueError(f"frames_per_chunk must be an integer in 1..16 (one attention tile), got {frames_per_chunk!r}")
         self.net = net
         self.B = B = batch_size
+        self.m = m = frames_per_chunk
         self.device = dev = torch.device(device)
-        n = net.stft_chunk_size + net.stft_pad_size
+        n = net.stft_chunk_size * m + net.stft_pad_size
         z = lambda *s, **k: torch.zeros(*s, device=dev, **k)
         self.chunk = z(B, net.num_ch, n)
         self.embed = z(B, net.spk_emb_dim)
-        self.out = z(B, net.n_srcs, net.stft_chunk_size)
+        self.out = z(B, net.n_srcs, net.stft_chunk_size * m)
         F_, C_, nh, H_ = net.n_freqs, net.emb_dim, net.n_head, net.hidden
         mk = lambda: dict(conv_buf=z(B, net.num_ch * 2, 2, F_), deconv_buf=z(B, C_, 2, F_),
                           istft_buf=z(B, net.n_srcs, F_ * 2, 1),
                           h=[z(1, B * F_, H_) for _ in range(net.n_blocks)], c=[z(1, B * F_, H_) for _ in range(net.n_blocks)])
         self.sets = [mk(), mk()]
-        rows = 1 + net.local_atten_len - 1 + KV_PAD_ROWS
+        rows = m + net.local_atten_len - 1 + KV_PAD_ROWS      # the ring is the first 49 + m of them, the rest stays zero
         self.rings = [(z(B * nh, rows, 2 * QK_PAD, dtype=torch.float16), z(B * nh, rows, 2 * net.V_dim * F_, dtype=torch.float16))
                       for _ in range(net.n_blocks)]
         self.pos = z(1, dtype=torch.int32)
@@ -75,8 +83,8 @@ class Streamer:
             # (tensor, version at build time) of every parameter / buffer: `step` re-checks a few per chunk, round robin
             self._versions = [] if net._blob is not None else [(t, t._version) for t in list(net.parameters()) + list(net.buffers())]
             self._vpos = 0
-            self._ws = net._workspace(B, 1, dev)
-            net._ws.pop((B, 1, str(dev)), None)          # private to this streamer from now on
+            self._ws = net._workspace(B, m, dev)
+            net._ws.pop((B, m, str(dev)), None)          # private to this streamer from now on
         if use_graph:
             self.graphs = self._capture(self._body, dev)
             self.graph = self.graphs[0]
@@ -106,7 +114,11 @@ class Streamer:
             # ring slot counter, kept in [0, window): an ever-growing int32 would go negative after 2^31 chunks and C's
             # `%` would then index before the ring.  One 1-thread kernel (two torch elementwise launches cost 9 us of the chunk)
             st = self.net._stream(self.device)
-            self.net._lib(self.pos).call("lh_ring_advance", self.pos.data_ptr(), self.net.local_atten_len, st)
+            if self.m == 1:
+                self.net._lib(self.pos).call("lh_ring_advance", self.pos.data_ptr(), self.net.local_atten_len, st)
+            else:
+                self.net._lib(self.pos).call("lh_ring_advance_by", self.pos.data_ptr(), self.m,
+                                             self.net.local_atten_len - 1 + self.m, st)
 
     def _carried(self, k: int) -> list:
         """What a chunk carries in ping-pong set k: the conv / deconv / iSTFT tails, every block's h, every block's c."""
@@ -130,7 +142,10 @@ class Streamer:
             self.net._speaker_gain(self.embed, self.gain_raw, self.gain)
 
     def step(self, chunk: torch.Tensor) -> torch.Tensor:
-        """chunk [B, 2, 192] (128 new + 64 look-ahead samples) -> [B, 2, 128]."""
+        """chunk [B, 2, 128 m + 64] (128 m new + 64 look-ahead samples) -> [B, 2, 128 m]."""
+        if chunk.shape[-1] != self.chunk.shape[-1]:
+            raise ValueError(f"a chunk of this streamer is {self.chunk.shape[-1]} samples "
+                             f"({self.net.stft_chunk_size} x {self.m} new + {self.net.stft_pad_size} look-ahead), got {chunk.shape[-1]}")
         self._check_repacked()
         if self.net.range_check and int(self.range_flag[0]) != 0:     # host read of the pinned word: free
             self.range_flag.zero_()
