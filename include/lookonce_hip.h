@@ -634,7 +634,7 @@ int lh_binaural_cues(const float* est, const float* gt, double* scratch, double*
  *   cmd        [2][S] words of LH_SESSION_* bits: row 0 posted by the host (one asynchronous copy ahead of the step), row 1
  *              posted by lh_session_end for the next chunk — separate words, so the host's copy cannot erase a RESET the
  *              device posted meanwhile.  lh_session_begin acts on row 0 | row 1; lh_session_end consumes both.
- *              Bits 8..30 of a host word with LH_SESSION_OPEN: the opening's generation (non-zero)
+ *              Bits 8..30 of a host word with LH_SESSION_OPEN: the opening's generation (non-zero; a field of 0 becomes 1)
  *   active     [S] 0 = idle, else the generation of the slot's current opening
  *   fault      [S] DEVICE-ACCESSIBLE words the host reads in place (pinned host memory, written with system-scope vector
  *              stores like the range flag above): set to the generation of the opening the device closed
@@ -666,12 +666,14 @@ int lh_session_end(const lh_span_t* spans, int n_spans, const float* chunk_in, f
  * words cmd [2][S] / active [S], whose stride stays S.  Call order of one chunk, all with the same n_rows:
  *   lh_session_move -> lh_session_begin_rows -> (lh_session_capture, by slot, S) -> the chunk's launches with B = n_rows ->
  *   lh_ring_advance -> lh_session_end_rows.
- *   from       [S] device words, the move table: from[d] = r + 1 copies row r over row d, 0 = nothing.  Posted by the host with
+ *   from       [S] device words, the move table: from[d] = r + 1 copies row r over row d; 0, d + 1 and every value outside
+ *              [1, S] = nothing.  Posted by the host with
  *              the other tables (one asynchronous copy ahead of the step), read by lh_session_move for d < n_rows, zeroed by
  *              lh_session_end_rows — a replay without a new table moves nothing.  The pairs of one launch must be disjoint:
  *              every source above, every destination below the host's new row count.
- *   slot_of    [S] row -> slot, negative = the row has no listener: it is idle whatever its words say (as if the host had
- *              posted CLOSE; a RESET the device posted on it is still served), reads no input and reports nothing
+ *   slot_of    [S] row -> slot, negative or not below S = the row has no listener: it is idle whatever its words say (the
+ *              host's word counts as CLOSE and nothing else; a RESET the device posted on it is still served), reads no
+ *              input and reports nothing; its `active` and command words are still written
  *   row_of     [S] slot -> row, negative = none
  *   lh_session_move       (grid over row x tile; spans = lh_session_begin's table plus the speaker gain) copies the row's slice
  *              of every span with 16-byte loads and stores, active[r] -> active[d] and cmd[1][r] -> cmd[1][d].  Bytes, not

@@ -389,7 +389,9 @@ __global__ void __launch_bounds__(SE_NT) k_session_end(SessSpans sp, SessSpans c
     for (int i = 0; i < SE_SP; ++i)
 #pragma unroll
         for (int u = 0; u < SE_U; ++u) bad |= nonfinite4(v[i][u]);
-    for (int i = 0; i < sp.n; ++i) {               // longer spans than the streamer's: the rest, the slow way
+    // longer spans than the streamer's: the rest, the slow way.  No streamer reaches this loop; the direct calls of
+    // tests/session_kernel_cases.py do, on the emulator and on the device, with probes at float4 2048, 2049 and n16 - 1
+    for (int i = 0; i < sp.n; ++i) {
         const long n16 = (long)(sp.s[i].bytes >> 4);
         const float4* q = reinterpret_cast<const float4*>(static_cast<const char*>(sp.s[i].base) +
                                                           (unsigned long long)r * sp.s[i].bytes);
